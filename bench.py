@@ -18,14 +18,20 @@ and carries the barriers):
           carry read by the kernel (carry_dev).  The step moves 4 + 8 B/elem
           and runs one collective at every N.
 
+A plain run (`--gpus N --steps K --warmup W`) sets up, warms up, times the K
+steps, writes the last step's outputs if `--dump-outputs DIR` is given and
+prints the result line.  Everything else described below (the per-element
+checks, the stand-alone scan, `ops`' other configs, `cpu_baseline`) runs only
+with `--full`.
+
 `value` = elements of the distributed vector processed per second by the
 whole job (N * 2^30 / step time).  `roofline` is for the dominant kernel (the
 scan): algorithmic 8 B/elem x elements per launch / mean launch time from HIP
 events recorded on the drhip stream the kernel runs on.  `traffic` is the
 PMC-measured HBM bytes per launch (profiles/pmc_summary.json, tools/pmc.sh).
 
-`ops` carries the other BASELINE configs, each timed the same way
-(--no-ops skips them): sort (C3: 2^28 uint32 keys per GPU, local radix sort +
+With `--full`, `ops` carries the other BASELINE configs, each timed the same
+way (--no-ops skips them): sort (C3: 2^28 uint32 keys per GPU, local radix sort +
 exact-splitting all-to-all for N > 1), gemv (C4: 2^26-row random CSR, 10
 nnz/row, rows split over the ranks, x all_gathered every call), stencil1d
 (C5: 2^29 cells per GPU, 3-point, halo exchange every step).
@@ -82,6 +88,10 @@ def parse():
     p.add_argument("--warmup", type=int, default=3)
     p.add_argument("--log2n", type=int, default=30, help="elements per GPU = 2^log2n")
     p.add_argument("--dtype", default="f32", choices=["f32", "i32"])
+    p.add_argument("--full", action="store_true",
+                   help="also run the checks, the stand-alone scan, the other configs (ops) and the CPU baseline")
+    p.add_argument("--dump-outputs", metavar="DIR", default=None,
+                   help="write the last timed step's outputs to DIR/<name>.npy")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--no-ops", action="store_true", help="skip the sort / gemv / stencil configs")
     p.add_argument("--only-ops", default="", help="comma list of ops to run (c2_int32,sort,gemv,stencil1d,for_each,dot,"
@@ -363,6 +373,39 @@ def timed_region(torch, dist, world, fn, steps):
     return dt / steps * 1e3
 
 
+DUMP_SAMPLE = 1 << 22  # scanned elements written by --dump-outputs (16 MB of float32)
+DUMP_SEED = 20240229
+
+
+def dump_outputs(torch, np, directory, rank, world, out, red_part, result):
+    """--dump-outputs: what the last timed step handed back, as .npy files
+    (rank r > 0 of an N > 1 job writes <name>.rank<r>.npy):
+      reduce.npy          the shp::reduce value, float64, shape (1,): the
+                          segment's partial at N = 1, the fold of all N at N > 1;
+      inclusive_scan.npy  this rank's scanned segment, float32 (float64 for
+                          i32, exact): all of it up to DUMP_SAMPLE elements,
+                          else the elements at DUMP_SAMPLE fixed positions
+                          (sorted draws of numpy's default_rng(DUMP_SEED) over
+                          the segment, the last one moved to the final
+                          element, which carries the whole range's sum).
+    Called after the timed region's final synchronize, before anything else
+    writes `out`."""
+    os.makedirs(directory, exist_ok=True)
+    sfx = "" if rank == 0 else f".rank{rank}"
+    n = out.numel()
+    if n > DUMP_SAMPLE:
+        idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, n, DUMP_SAMPLE))
+        idx[-1] = n - 1
+        scanned = out[torch.from_numpy(idx).to(out.device)]
+    else:
+        scanned = out
+    wide = np.float32 if out.dtype == torch.float32 else np.float64
+    np.save(os.path.join(directory, f"inclusive_scan{sfx}.npy"), scanned.cpu().numpy().astype(wide))
+    red = red_part if world == 1 else result
+    np.save(os.path.join(directory, f"reduce{sfx}.npy"), red.cpu().numpy().astype(np.float64))
+    log(f"outputs written to {directory}")
+
+
 def self_launch(args):
     """`bench.py --gpus N` (N > 1) started without a launcher: start N ranks
     with torch.distributed.run as a CHILD process (nothing here has touched
@@ -481,43 +524,15 @@ def main():
     ms_red, ms_scan = T.ms("reduce"), T.ms("scan")
     isz = dt_np.itemsize
 
-    # the standalone single-pass scan (drhip_inclusive_scan: decoupled
-    # look-back, what a scan without a preceding reduce of its range runs),
-    # timed on the same input for comparison
-    with torch.cuda.stream(stream):
-        for _ in range(2):
-            drhip.scan_async(0, dt_np, "plus", x.data_ptr(), out.data_ptr(), n)
-        for _ in range(max(3, min(args.steps, 10))):
-            T("scan_single_pass", lambda: drhip.scan_async(0, dt_np, "plus", x.data_ptr(), out.data_ptr(), n))
-    torch.cuda.synchronize()
-    ms_sp = T.ms("scan_single_pass")
-    # checks (outside the timed region, independent of the oracle): the
-    # reduce vs torch's fp64 sum, EVERY scanned element vs torch's fp64
-    # cumsum (f32: rel <= 1e-5) or its wrapped int64 cumsum (i32: exact),
-    # for the step's output (rerun: the timing loop above overwrote `out`)
-    with torch.cuda.stream(stream):
-        step(False)
-        drhip.reduce_async(0, dt_np, "plus", x.data_ptr(), n, red_part.data_ptr())
-    torch.cuda.synchronize()
-    carry_chk = None
-    if world > 1 and rank > 0:  # the carry the scan folded: the gathered partials of ranks < rank
-        carry_chk = gathered[:rank].double().sum().to(acc_t).reshape(1) if args.dtype == "f32" else \
-            gathered[:rank].long().sum().reshape(1)
-    check = all_ranks(torch, dist, world, check_reduce_scan(torch, x, out, red_part, carry_chk, world, rank,
-                                                            args.dtype))
-    if world > 1:
-        tot = float(gathered.double().sum().item()) if args.dtype == "f32" else int(gathered.long().sum().item())
-        check["reduce_result_ok"] = bool(abs(float(result.item()) - tot) <= 1e-9 * max(1.0, abs(tot))) \
-            if args.dtype == "f32" else (int(result.item()) - tot) % (1 << 32) == 0
-        check["ok"] = check["ok"] and check["reduce_result_ok"]
-    del out, x
-    torch.cuda.empty_cache()
+    if args.dump_outputs:
+        dump_outputs(torch, np, args.dump_outputs, rank, world, out, red_part, result)
 
     scan_bytes = 2 * isz * n
     achieved = scan_bytes / (ms_scan * 1e-3) / 1e9
     # the instantiations the 2^30 step launches (big tiles: 32 vectors per thread)
     ctype = "float" if args.dtype == "f32" else "int"
     scan_kname = f"scan_wave_given_kernel<0, {ctype}, true, 32, 256>"
+    # the step's two kernels, from the HIP events the timed steps recorded
     ops = {
         "reduce": {"ms": ms_red, "elements_per_s": n / (ms_red * 1e-3),
                    "GBps": isz * n / (ms_red * 1e-3) / 1e9,
@@ -527,10 +542,43 @@ def main():
         "inclusive_scan": {"ms": ms_scan, "elements_per_s": n / (ms_scan * 1e-3), "GBps": achieved,
                            "frac": achieved / HBM_PEAK_GBS,
                            "kernel": "scan_wave_given_kernel (tile-part prefixes from the step's reduce: no look-back, no LDS, no barrier)"},
-        "inclusive_scan_single_pass": {"ms": ms_sp, "frac": scan_bytes / (ms_sp * 1e-3) / 1e9 / HBM_PEAK_GBS,
-                                       "kernel": "scan_kernel (decoupled look-back; drhip_inclusive_scan alone)"},
     }
-    if not args.no_ops:
+    check = None
+    if args.full:
+        # the standalone single-pass scan (drhip_inclusive_scan: decoupled
+        # look-back, what a scan without a preceding reduce of its range runs),
+        # timed on the same input for comparison
+        with torch.cuda.stream(stream):
+            for _ in range(2):
+                drhip.scan_async(0, dt_np, "plus", x.data_ptr(), out.data_ptr(), n)
+            for _ in range(max(3, min(args.steps, 10))):
+                T("scan_single_pass", lambda: drhip.scan_async(0, dt_np, "plus", x.data_ptr(), out.data_ptr(), n))
+        torch.cuda.synchronize()
+        ms_sp = T.ms("scan_single_pass")
+        ops["inclusive_scan_single_pass"] = {"ms": ms_sp, "frac": scan_bytes / (ms_sp * 1e-3) / 1e9 / HBM_PEAK_GBS,
+                                             "kernel": "scan_kernel (decoupled look-back; drhip_inclusive_scan alone)"}
+        # checks (outside the timed region, independent of the oracle): the
+        # reduce vs torch's fp64 sum, EVERY scanned element vs torch's fp64
+        # cumsum (f32: rel <= 1e-5) or its wrapped int64 cumsum (i32: exact),
+        # for the step's output (rerun: the timing loop above overwrote `out`)
+        with torch.cuda.stream(stream):
+            step(False)
+            drhip.reduce_async(0, dt_np, "plus", x.data_ptr(), n, red_part.data_ptr())
+        torch.cuda.synchronize()
+        carry_chk = None
+        if world > 1 and rank > 0:  # the carry the scan folded: the gathered partials of ranks < rank
+            carry_chk = gathered[:rank].double().sum().to(acc_t).reshape(1) if args.dtype == "f32" else \
+                gathered[:rank].long().sum().reshape(1)
+        check = all_ranks(torch, dist, world, check_reduce_scan(torch, x, out, red_part, carry_chk, world, rank,
+                                                                args.dtype))
+        if world > 1:
+            tot = float(gathered.double().sum().item()) if args.dtype == "f32" else int(gathered.long().sum().item())
+            check["reduce_result_ok"] = bool(abs(float(result.item()) - tot) <= 1e-9 * max(1.0, abs(tot))) \
+                if args.dtype == "f32" else (int(result.item()) - tot) % (1 << 32) == 0
+            check["ok"] = check["ok"] and check["reduce_result_ok"]
+    del out, x
+    torch.cuda.empty_cache()
+    if args.full and not args.no_ops:
         ops.update(extra_ops(args, torch, dist, np, drhip, dr_dist, stream, world, rank))
 
     res = {
@@ -564,10 +612,12 @@ def main():
                      "algorithmic_bytes_per_launch": scan_bytes,
                      "launch_ms": ms_scan},
         "ops": ops,
-        "check": check,
+        "full": args.full,
     }
+    if args.full:
+        res["check"] = check
     log("ops done")
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         res["cpu_baseline"] = cpu_baseline(args.dtype)
     elif rank == 0:
         res["cpu_baseline"] = None

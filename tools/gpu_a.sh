@@ -9,7 +9,9 @@ if [ -n "$REHEARSE" ]; then
   rc=$?; tail -c 3000 gpurun_out/bench2.log; [ $rc -eq 0 ] || exit $rc
 fi
 if [ -n "$OPS" ]; then
-  timeout -k 10 200 python -u bench.py --steps 5 --warmup 2 --only-ops $OPS --no-cpu-baseline > gpurun_out/bench_a.log 2>&1
-  rc=$?; tail -c 2500 gpurun_out/bench_a.log; [ $rc -eq 0 ] || exit $rc
+  LOG=${LOG_DIR:-bench_out}/bench_a.log
+  mkdir -p "$(dirname "$LOG")"
+  timeout -k 10 200 python -u bench.py --full --steps 5 --warmup 2 --only-ops $OPS --no-cpu-baseline > "$LOG" 2>&1
+  rc=$?; tail -c 2500 "$LOG"; [ $rc -eq 0 ] || exit $rc
 fi
 exit 0

@@ -2,6 +2,8 @@
 # GPU round: parity tests, bench, rocprof kernel-trace summary.
 # Each GPU step has its own time limit; a fault/abort/timeout ends the script.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
+# the per-op figures, checks and the CPU baseline are behind bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS}"
 R=$(pwd)
 mkdir -p gpurun_out
 ok() { local rc=$1; [ $rc -eq 0 ] || [ $rc -eq 1 ]; }

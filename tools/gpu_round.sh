@@ -2,6 +2,8 @@
 # One GPU pass: chosen pytest files (-m gpu), then bench.py; each step under
 # its own time limit, stop at the first failure.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
+# the per-op figures, checks and the CPU baseline are behind bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS}"
 mkdir -p gpurun_out
 TESTS=${TESTS:-tests}
 if [ -n "$TESTS" ] && [ "$TESTS" != "none" ]; then

@@ -1,6 +1,8 @@
 #!/bin/bash
 # Two separate PMC passes (FETCH_SIZE, WRITE_SIZE) over a short bench run.
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
+# the per-op figures, checks and the CPU baseline are behind bench.py --full
+BENCH_ARGS="--full ${BENCH_ARGS}"
 R=$(pwd)
 export TMPDIR=/tmp
 rm -rf gpurun_out/pmc_fetch gpurun_out/pmc_write

@@ -16,7 +16,7 @@ for op in gemv_banded gemv_random sort; do
   for c in FETCH_SIZE WRITE_SIZE; do
     rm -rf gpurun_out/pmc_${op}_$c
     timeout -s KILL 180 rocprofv3 --pmc $c -d "$R/gpurun_out/pmc_${op}_$c" -o pmc --output-format csv \
-      -- python3 "$R/bench.py" --steps 2 --warmup 1 --no-cpu-baseline --only-ops $op --log2n 20 \
+      -- python3 "$R/bench.py" --full --steps 2 --warmup 1 --no-cpu-baseline --only-ops $op --log2n 20 \
       > gpurun_out/pmc_${op}_$c.log 2>&1 || exit $?
   done
 done

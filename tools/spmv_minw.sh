@@ -5,7 +5,7 @@ cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 for v in base minw8 base minw8; do
   lib=""; [ "$v" = minw8 ] && lib="$PWD/tools/diag/minw8/libdrhip.so"
-  DRHIP_LIB=$lib timeout -k 10 200 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline \
+  DRHIP_LIB=$lib timeout -k 10 200 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline \
     --only-ops gemv_banded,gemv > gpurun_out/spmv_$v.log 2>&1 || exit $?
   python3 - "gpurun_out/spmv_$v.log" "$v" <<'PY'
 import json, sys

@@ -3,7 +3,7 @@
 cd "${GRAFT_REPO_ROOT:-/root/repo}"
 mkdir -p gpurun_out
 for v in 0 1 2 3 0; do
-  DRHIP_ST_NT=$v timeout -k 10 200 python -u bench.py --steps 10 --warmup 3 --no-cpu-baseline \
+  DRHIP_ST_NT=$v timeout -k 10 200 python -u bench.py --full --steps 10 --warmup 3 --no-cpu-baseline \
     --only-ops stencil1d,stencil2d > gpurun_out/stnt_$v.log 2>&1 || exit $?
   python3 - "gpurun_out/stnt_$v.log" "$v" <<'PY'
 import json, sys
