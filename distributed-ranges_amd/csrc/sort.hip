@@ -231,67 +231,14 @@ __device__ __forceinline__ void rank_keys(const U (&key)[KPL], uint32_t (&rank2)
 // same-address lane pairs out of order; checked again on every device before
 // the first sort uses it, sort_rank_atomic below), so slot-by-slot issue
 // gives the stable rank.  Replaces 8 ballots + 16 bit-ops + a counter read
-// and write per key.
-// DRHIP_SORT_UNI_FAST = 1: a wave whose keys all share the digit being
-// ranked or counted takes ONE LDS update instead of 64 same-address atomics
-// per round (skewed keys: tools/r06/sort_skew_probe.py)
-#ifndef DRHIP_SORT_UNI_FAST
-#define DRHIP_SORT_UNI_FAST 1
-#endif
-constexpr bool kSortUniFast = DRHIP_SORT_UNI_FAST;
-// DRHIP_SORT_UNI_NXT = 1: the same for the next-digit count of the
-// persistent onesweep's write-out (one check per round of every wave)
-#ifndef DRHIP_SORT_UNI_NXT
-#define DRHIP_SORT_UNI_NXT 0
-#endif
-constexpr bool kSortUniNxt = DRHIP_SORT_UNI_NXT;
-// DRHIP_SORT_FEW_K = K > 0 (measurement knob, default 0): a wave whose first
-// round holds at most K distinct digits (the exponent byte of floats: a few
-// values per wave) ranks / counts those digits with ballots into K
-// wave-uniform counters -- no LDS atomic, whose same-address lanes would
-// serialise -- and only the other digits' keys with atomics.  K = 4: f32
-// U[0,1) keys 3.66 -> 3.16 ms at 2^28, but uniform keys 3 % slower (the
-// per-tile probe), so it stays off (profiles/r06x_sort_few_ab.txt).
-#ifndef DRHIP_SORT_FEW_K
-#define DRHIP_SORT_FEW_K 0
-#endif
-constexpr int kSortFewK = DRHIP_SORT_FEW_K;
-constexpr int kFewN = kSortFewK > 0 ? kSortFewK : 1; // array extent
-// DRHIP_SORT_FEW_HIST = 1: the same for the pre-pass counts (a per-tile probe
-// of every position; no histogram is known yet)
-#ifndef DRHIP_SORT_FEW_HIST
-#define DRHIP_SORT_FEW_HIST 0
-#endif
-constexpr bool kSortFewHist = DRHIP_SORT_FEW_HIST;
-
-// The first distinct values of v over the wave's lanes, in lane order, into
-// c[0..K) (wave-uniform); returns how many (K + 1: more than K exist).
-template <int K> __device__ __forceinline__ int wave_distinct(unsigned v, unsigned (&c)[K]) {
-  uint64_t todo = __ballot(1);
-  int n = 0;
-#pragma unroll
-  for (int k = 0; k < K; k++) {
-    c[k] = 0xFFFFFFFFu; // matches no digit
-    if (todo) {
-      const int l0 = __builtin_ctzll(todo);
-      const unsigned dl = __builtin_amdgcn_readlane(v, l0);
-      c[k] = dl;
-      n = k + 1;
-      todo &= ~__ballot(v == dl);
-    }
-  }
-  return todo ? K + 1 : n;
-}
-
-__device__ __forceinline__ uint32_t lanes_below(uint64_t m) {
-  return __builtin_amdgcn_mbcnt_hi((unsigned)(m >> 32), __builtin_amdgcn_mbcnt_lo((unsigned)m, 0u));
-}
-
+// and write per key.  A wave whose keys all share the digit being ranked (or,
+// in radix_tile_hist0, counted) takes ONE LDS update instead of 64
+// same-address atomics per round (skewed keys: tools/r06/sort_skew_probe.py).
 template <typename U, int KPL, int KPW>
 __device__ __forceinline__ void rank_keys_atomic(const U (&key)[KPL], uint32_t (&rank2)[(KPL + 1) / 2],
                                                  unsigned valid, int shift, uint32_t (&wcnt)[kDigits1], int lane,
-                                                 int wid, bool few_ok = true) {
-  if constexpr (kSortUniFast) {
+                                                 int wid) {
+  { // (a scope of its own: the test's locals end here, which the generated code depends on)
     // every key of this wave valid and of ONE digit (small integers' high
     // bytes, constant fields): the atomic path would serialise 64 lanes on
     // one LDS counter per round; the ranks it returns are r * 64 + lane
@@ -316,46 +263,6 @@ __device__ __forceinline__ void rank_keys_atomic(const U (&key)[KPL], uint32_t (
       return;
     }
   }
-  if constexpr (kSortFewK > 0) {
-    // at most kSortFewK distinct digits in the first round: those digits get
-    // their ranks from ballots (rank = the digit's count in earlier rounds +
-    // its lanes below this one: the atomics' order), any other digit from
-    // the atomics; each digit takes one of the two ways for the whole tile
-    unsigned cand[kFewN];
-    const unsigned dr0 = wid * KPW + lane < valid ? (unsigned)(key[0] >> shift) & 0xFF : (unsigned)kRadix;
-    const int nd = few_ok ? wave_distinct<kFewN>(dr0, cand) : kSortFewK + 1;
-    if (nd <= kSortFewK) {
-      uint32_t run[kFewN];
-#pragma unroll
-      for (int k = 0; k < kSortFewK; k++) run[k] = 0;
-#pragma unroll
-      for (int r = 0; r < KPL; r++) {
-        const unsigned li = wid * KPW + r * kWave + lane;
-        const unsigned d = li < valid ? (unsigned)(key[r] >> shift) & 0xFF : (unsigned)kRadix;
-        uint32_t rk = 0;
-        bool hit = false;
-#pragma unroll
-        for (int k = 0; k < kSortFewK; k++) {
-          const uint64_t m = __ballot(d == cand[k]);
-          if (d == cand[k]) {
-            rk = run[k] + lanes_below(m);
-            hit = true;
-          }
-          run[k] += (uint32_t)__builtin_popcountll(m);
-        }
-        if (!hit) rk = atomicAdd(&wcnt[d], 1u);
-        if (r & 1) rank2[r / 2] |= rk << 16;
-        else rank2[r / 2] = rk;
-        __builtin_amdgcn_sched_barrier(0); // one round's ballots live at a time
-      }
-      if (lane == 0) {
-#pragma unroll
-        for (int k = 0; k < kSortFewK; k++)
-          if (k < nd) wcnt[cand[k]] += run[k];
-      }
-      return;
-    }
-  }
 #pragma unroll
   for (int r = 0; r < KPL; r++) {
     const unsigned li = wid * KPW + r * kWave + lane;
@@ -368,10 +275,9 @@ __device__ __forceinline__ void rank_keys_atomic(const U (&key)[KPL], uint32_t (
 
 template <bool AR, typename U, int KPL, int KPW>
 __device__ __forceinline__ void rank_subtile(const U (&key)[KPL], uint32_t (&rank2)[(KPL + 1) / 2], unsigned valid,
-                                             unsigned full, int shift, uint32_t (&wcnt)[kDigits1], int lane, int wid,
-                                             bool few_ok = true) {
+                                             unsigned full, int shift, uint32_t (&wcnt)[kDigits1], int lane, int wid) {
   if constexpr (AR) {
-    rank_keys_atomic<U, KPL, KPW>(key, rank2, valid, shift, wcnt, lane, wid, few_ok);
+    rank_keys_atomic<U, KPL, KPW>(key, rank2, valid, shift, wcnt, lane, wid);
   } else {
     if (valid == full) rank_keys<U, KPL, KPW, 8>(key, rank2, valid, shift, wcnt, lane, wid);
     else rank_keys<U, KPL, KPW, 9>(key, rank2, valid, shift, wcnt, lane, wid);
@@ -614,47 +520,26 @@ __global__ __launch_bounds__(NT) void radix_tile_hist0(const typename KeyBits<DT
     }
     __syncthreads();
     unsigned uni = 0;
-    if constexpr (kSortUniFast) {
-      // a full tile whose wave holds ONE digit at position p: one LDS add for
-      // the wave's NV * V * 64 keys instead of 64 same-address atomics per key
-      if (valid == (unsigned)SUB) {
+    // a full tile whose wave holds ONE digit at position p: one LDS add for
+    // the wave's NV * V * 64 keys instead of 64 same-address atomics per key
+    if (valid == (unsigned)SUB) {
 #pragma unroll
-        for (int p = 0; p < NCNT; p++) {
-          // the first key of every lane first (3 instructions for keys that
-          // differ), then the rest
-          const unsigned d0 = (unsigned)(KeyBits<DT>::in(x[0].v[0]) >> (8 * p)) & 0xFF;
-          const unsigned dw = __builtin_amdgcn_readfirstlane(d0);
-          bool same = false;
-          if (__all(d0 == dw)) {
-            same = true;
+      for (int p = 0; p < NCNT; p++) {
+        // the first key of every lane first (3 instructions for keys that
+        // differ), then the rest
+        const unsigned d0 = (unsigned)(KeyBits<DT>::in(x[0].v[0]) >> (8 * p)) & 0xFF;
+        const unsigned dw = __builtin_amdgcn_readfirstlane(d0);
+        bool same = false;
+        if (__all(d0 == dw)) {
+          same = true;
 #pragma unroll
-            for (int r = 0; r < NV; r++)
+          for (int r = 0; r < NV; r++)
 #pragma unroll
-              for (int j = 0; j < V; j++) same = same && ((unsigned)(KeyBits<DT>::in(x[r].v[j]) >> (8 * p)) & 0xFF) == dw;
-          }
-          if (__all(same)) {
-            uni |= 1u << p;
-            if (lane == 0) s_cnt[p][wid][dw] += (uint32_t)(NV * V * kWave);
-          }
+            for (int j = 0; j < V; j++) same = same && ((unsigned)(KeyBits<DT>::in(x[r].v[j]) >> (8 * p)) & 0xFF) == dw;
         }
-      }
-    }
-    // positions whose first keys show at most kSortFewK digits across the
-    // wave: ballot counts into wave-uniform counters, atomics only for the
-    // other digits (full tiles)
-    unsigned few = 0;
-    unsigned cand[NCNT][kFewN];
-    uint32_t run[NCNT][kFewN];
-    if constexpr (kSortFewK > 0 && kSortFewHist) {
-      if (valid == (unsigned)SUB) {
-#pragma unroll
-        for (int p = 0; p < NCNT; p++) {
-#pragma unroll
-          for (int k = 0; k < kSortFewK; k++) run[p][k] = 0;
-          if (!(uni >> p & 1u)) {
-            const unsigned d0 = (unsigned)(KeyBits<DT>::in(x[0].v[0]) >> (8 * p)) & 0xFF;
-            if (wave_distinct<kFewN>(d0, cand[p]) <= kSortFewK) few |= 1u << p;
-          }
+        if (__all(same)) {
+          uni |= 1u << p;
+          if (lane == 0) s_cnt[p][wid][dw] += (uint32_t)(NV * V * kWave);
         }
       }
     }
@@ -663,46 +548,9 @@ __global__ __launch_bounds__(NT) void radix_tile_hist0(const typename KeyBits<DT
       const unsigned vi = r * NT + tid;
       if ((vi + 1) * V <= valid) {
 #pragma unroll
-        for (int j = 0; j < V; j++) {
-          if constexpr (kSortFewK > 0 && kSortFewHist) {
-            if (few) {
-              const U k = KeyBits<DT>::in(x[r].v[j]);
-#pragma unroll
-              for (int p = 0; p < NCNT; p++) {
-                if (uni >> p & 1u) continue;
-                const unsigned dp = (unsigned)(k >> (8 * p)) & 0xFF;
-                if (few >> p & 1u) {
-                  bool hit = false;
-#pragma unroll
-                  for (int c = 0; c < kSortFewK; c++) {
-                    const uint64_t m = __ballot(dp == cand[p][c]);
-                    hit = hit || dp == cand[p][c];
-                    run[p][c] += (uint32_t)__builtin_popcountll(m);
-                  }
-                  if (!hit) atomicAdd(&s_cnt[p][wid][dp], 1u);
-                } else {
-                  atomicAdd(&s_cnt[p][wid][dp], 1u);
-                }
-              }
-              __builtin_amdgcn_sched_barrier(0);
-              continue;
-            }
-          }
-          count(x[r].v[j], uni);
-        }
+        for (int j = 0; j < V; j++) count(x[r].v[j], uni);
       } else {
         for (unsigned e = vi * V; e < valid && e < (vi + 1) * V; e++) count(keys[sbase + e], 0u);
-      }
-    }
-    if constexpr (kSortFewK > 0 && kSortFewHist) {
-      if (few && lane == 0) {
-#pragma unroll
-        for (int p = 0; p < NCNT; p++)
-          if (few >> p & 1u) {
-#pragma unroll
-            for (int c = 0; c < kSortFewK; c++)
-              if (cand[p][c] < (unsigned)kRadix) s_cnt[p][wid][cand[p][c]] += run[p][c];
-          }
       }
     }
   } else {
@@ -1011,13 +859,7 @@ __global__ __launch_bounds__(kSortThreads, (OsCfg<typename KeyBits<DT>::U, BIG>:
     if (p < valid) {
       const U k = sm.keys[p];
       const unsigned d = (unsigned)(k >> shift) & 0xFF;
-#if defined(DRHIP_SORT_WRITE_MODE) && DRHIP_SORT_WRITE_MODE == 0 // measurement: no global stores
-      if (k == (U)0x9E3779B9u && n == 3) dst[p] = k;
-#elif defined(DRHIP_SORT_WRITE_MODE) && DRHIP_SORT_WRITE_MODE == 2 // measurement: coalesced stores
-      dst[sbase + p] = XOUT ? KeyBits<DT>::out(k) : k + (U)s_run[d];
-#else
       dst[s_run[d] + p] = XOUT ? KeyBits<DT>::out(k) : k;
-#endif
       if (NXT && kCntWO) atomicAdd(&s_nxt[wid][(unsigned)(k >> (shift + 8)) & 0xFF], 1u);
     }
   }
@@ -1053,14 +895,6 @@ __global__ __launch_bounds__(kSortThreads, (OsCfg<typename KeyBits<DT>::U, BIG>:
 // write-out ran slower (pass 0 0.60 -> 0.67 ms): the passes are bound by
 // the memory system under the scattered stores, not by load latency.
 constexpr int kOsGroup = 64;
-// DRHIP_SORT_EARLY_PUB=1 (measurement knob): passes 1-3 publish a tile's
-// digit counts (AGG) from the per-wave counts right after ranking, before
-// the digit scan.  Round 5, 2^28 u32, interleaved with the default on one
-// box (profiles/r05_sort_early_pub_ab.txt): see DESIGN 4.0.
-#ifndef DRHIP_SORT_EARLY_PUB
-#define DRHIP_SORT_EARLY_PUB 0
-#endif
-constexpr bool kOsEarlyPub = DRHIP_SORT_EARLY_PUB;
 #ifndef DRHIP_SORT_P0_ONESHOT
 #define DRHIP_SORT_P0_ONESHOT 0
 #endif
@@ -1101,18 +935,6 @@ __global__ __launch_bounds__(NT, (OsCfg<typename KeyBits<DT>::U, BIG, NT>::MINW)
   // same XCD grouping under round-robin dispatch (b -> XCD b % 8; a wrong
   // guess only loses the grouping, never correctness)
   constexpr bool ONESHOT = XIN && kOsP0OneShot;
-  // the few-digit ranking (kSortFewK) only in a pass whose histogram has a
-  // digit holding at least a quarter of the keys (dstart: this position's
-  // digit starts over the whole input): no per-tile probe otherwise
-  bool few_ok = false;
-  if constexpr (kSortFewK > 0) {
-    __shared__ uint32_t s_maxc;
-    if (tid == 0) s_maxc = 0;
-    __syncthreads();
-    if (d < kRadix) atomicMax(&s_maxc, (d < kRadix - 1 ? dstart[d + 1] : (uint32_t)n) - dstart[d]);
-    __syncthreads();
-    few_ok = (size_t)s_maxc * 4 >= n;
-  }
   bool done_once = false;
   while (true) {
     if (tid == 0) {
@@ -1135,21 +957,8 @@ __global__ __launch_bounds__(NT, (OsCfg<typename KeyBits<DT>::U, BIG, NT>::MINW)
     U key[KPL];
     load_subtile<DT, XIN, KPL, KPW>(key, src, sbase, valid, lane, wid);
     uint32_t rank2[(KPL + 1) / 2];
-    rank_subtile<AR, U, KPL, KPW>(key, rank2, valid, (unsigned)SUB, shift, sm.wcnt[wid], lane, wid, few_ok);
+    rank_subtile<AR, U, KPL, KPW>(key, rank2, valid, (unsigned)SUB, shift, sm.wcnt[wid], lane, wid);
     __syncthreads();
-    if constexpr (kOsEarlyPub) {
-      // the tile's digit counts (AGG) straight from the per-wave counts,
-      // before the digit scan's two barriers (measurement knob, see kOsEarlyPub)
-      if (!XIN && tile && d < kRadix) {
-        uint32_t c = 0;
-#pragma unroll
-        for (int ww = 0; ww < NW; ww++) c += sm.wcnt[ww][d];
-        __hip_atomic_store(status + (size_t)tile * kRadix + d, f_agg | c, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if (local)
-          __hip_atomic_store(lstatus + (size_t)tile * kRadix + d, (uint32_t)(f_agg | c), __ATOMIC_RELAXED,
-                             __HIP_MEMORY_SCOPE_WORKGROUP);
-      }
-    }
     digit_offsets(sm, tid);
     // thread d < 256 owns digit d's publication, look-back and cursor
     const bool dig = d < kRadix;
@@ -1170,7 +979,7 @@ __global__ __launch_bounds__(NT, (OsCfg<typename KeyBits<DT>::U, BIG, NT>::MINW)
       __hip_atomic_store(row, word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
       if (local) __hip_atomic_store(lrow, (uint32_t)word, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     };
-    if (!XIN && dig && !(kOsEarlyPub && tile)) publish((tile ? f_agg : f_incl) | cnt);
+    if (!XIN && dig) publish((tile ? f_agg : f_incl) | cnt);
     if (status_next && dig) status_next[(size_t)tile * kRadix + d] = 0u;
     if (lstatus_next && dig) lstatus_next[(size_t)tile * kRadix + d] = 0u;
     long t = (long)tile - 1;
@@ -1222,25 +1031,10 @@ __global__ __launch_bounds__(NT, (OsCfg<typename KeyBits<DT>::U, BIG, NT>::MINW)
       const unsigned p = r * NT + tid;
       if (p < valid) {
         const U k = sm.keys[p];
-#if defined(DRHIP_SORT_NT_STORE) && DRHIP_SORT_NT_STORE // measurement: nontemporal write-out
-        __builtin_nontemporal_store(XOUT ? KeyBits<DT>::out(k) : k, dst + s_run[(unsigned)(k >> shift) & 0xFF] + p);
-#else
         dst[s_run[(unsigned)(k >> shift) & 0xFF] + p] = XOUT ? KeyBits<DT>::out(k) : k;
-#endif
         if (NXT) {
           const unsigned nd = (unsigned)(k >> (shift + 8)) & 0xFF;
-          if constexpr (kSortUniNxt) {
-            // the wave's active lanes all on one next digit: one add
-            const unsigned ndw = __builtin_amdgcn_readfirstlane(nd);
-            if (__all(nd == ndw)) {
-              if (__builtin_amdgcn_readfirstlane(lane) == (unsigned)lane)
-                atomicAdd(&s_nxt[wid][ndw], (uint32_t)__builtin_popcountll(__ballot(1)));
-            } else {
-              atomicAdd(&s_nxt[wid][nd], 1u);
-            }
-          } else {
-            atomicAdd(&s_nxt[wid][nd], 1u);
-          }
+          atomicAdd(&s_nxt[wid][nd], 1u);
         }
       }
     }

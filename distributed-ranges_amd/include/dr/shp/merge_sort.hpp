@@ -48,6 +48,12 @@ template <typename T> constexpr std::size_t padded(std::size_t e) {
 #ifndef DR_SHP_MSORT_SORT_THREADS
 #define DR_SHP_MSORT_SORT_THREADS 256
 #endif
+// the first merge pass takes runs of sort_tile and cuts its output into
+// tiles of kMsBlock * ipt: with a run that is not a multiple of that tile an
+// output tile spans two pairs of runs and merge_kernel merges the wrong
+// elements, silently
+static_assert(DR_SHP_MSORT_SORT_THREADS >= kMsBlock && (DR_SHP_MSORT_SORT_THREADS & (DR_SHP_MSORT_SORT_THREADS - 1)) == 0,
+              "DR_SHP_MSORT_SORT_THREADS must be a power of two and at least kMsBlock");
 template <typename T> constexpr int sort_threads() {
   return padded<T>(std::size_t(DR_SHP_MSORT_SORT_THREADS) * ipt<T>()) * sizeof(T) <= 65536 ? DR_SHP_MSORT_SORT_THREADS
                                                                                          : kMsBlock;

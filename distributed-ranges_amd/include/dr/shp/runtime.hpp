@@ -108,11 +108,11 @@ inline pinned_pool &host_pool() {
   return pool;
 }
 
-// Per-segment device scratch (the look-back scan's tile status words, the
-// sort's key/histogram workspace): grown on first use to the largest size
-// asked for and reused, so repeated algorithm calls allocate nothing.  Work
-// that uses it is enqueued on the segment's own stream, so consecutive users
-// are ordered by that stream.  Released by finalize().
+// Per-segment device scratch (the sort's key/histogram workspace): grown on
+// first use to the largest size asked for and reused, so repeated algorithm
+// calls allocate nothing.  Work that uses it is enqueued on the segment's own
+// stream, so consecutive users are ordered by that stream.  Released by
+// finalize().
 struct device_scratch_pool {
   std::vector<std::pair<void *, std::size_t>> per_rank;
   void *get(std::size_t rank, std::size_t bytes) {
@@ -137,8 +137,8 @@ inline device_scratch_pool &device_scratch() {
   static device_scratch_pool pool;
   return pool;
 }
-// The look-back scans' status buffers (dr/shp/scan.hpp DR_SHP_LB_EPOCH): one
-// per segment, owned by the look-back scans alone (another user's bytes there
+// The look-back scans' status buffers (dr/shp/scan.hpp "Epochs"): one per
+// segment, owned by the look-back scans alone (another user's bytes there
 // could carry a live epoch's tag).  Every call takes the next epoch.  Two
 // layouts share the buffer: T <= 12 bytes publishes {value, tag} 8-B words at
 // fixed 128-B granules (every granule word's high half only ever holds a
@@ -151,11 +151,6 @@ inline device_scratch_pool &device_scratch() {
 // are ordered by its stream.
 #ifndef DR_SHP_LB_EPOCH_MAX
 #define DR_SHP_LB_EPOCH_MAX ((1u << 30) - 1) // tests build a small wrap to exercise the clear
-#endif
-// test builds only: DR_SHP_LB_LAYOUT_CLEAR=0 drops the layout rule above (the
-// ScanStatusLayoutSwitch test then shows a small-T value read as a tag)
-#ifndef DR_SHP_LB_LAYOUT_CLEAR
-#define DR_SHP_LB_LAYOUT_CLEAR 1
 #endif
 struct lb_status_pool {
   struct entry {
@@ -177,10 +172,10 @@ struct lb_status_pool {
       check(drhip_malloc(static_cast<int>(rank), cap, &e.p), "drhip_malloc");
       e.cap = cap;
     }
-    if (DR_SHP_LB_LAYOUT_CLEAR && large) {
+    if (large) {
       hip_check(hipMemsetAsync(e.p, 0, tag_bytes, st), "scan status clear");
       e.epoch = 0;
-    } else if (e.epoch == 0 || e.epoch >= DR_SHP_LB_EPOCH_MAX || (DR_SHP_LB_LAYOUT_CLEAR && e.large)) {
+    } else if (e.epoch == 0 || e.epoch >= DR_SHP_LB_EPOCH_MAX || e.large) {
       hip_check(hipMemsetAsync(e.p, 0, e.cap, st), "scan status clear");
       e.epoch = 0;
     }

@@ -18,13 +18,39 @@
 //   tile = 256 threads x U slots x V elements; V consecutive elements per
 //   slot when both ranges are 16-byte-aligned contiguous spans of T (one
 //   16-B nontemporal load/store per slot), V = 1 through the accessors of
-//   any other view (coalesced element loads);
+//   any other view (coalesced element loads).  A full aligned tile is loaded
+//   with buffer loads, the slot offset in the SGPR soffset: one voffset VGPR
+//   for all U slots, where a global load needs a 64-bit address per slot
+//   (u * 4 KiB exceeds the 13-bit immediate) -- the C-ABI scan's load
+//   (csrc/scan_kernel.hpp scan_load);
 //   in-thread scan of each slot's V elements; per-slot wave scan by DPP
 //   row_shr / row_bcast moves, applied only where the source lane exists
 //   (no identity element is needed); wave 0 scans the U x 4 piece totals in
 //   element order and runs the look-back: the 64 lanes read 64 predecessor
 //   status granules at once and fold them in tile order with an ordered
 //   butterfly (higher lane = earlier tile on the left).
+//   Early aggregate: a full tile after the first publishes its aggregate
+//   BEFORE the per-slot wave scans, so its successors' look-backs wait less.
+//   It is an ORDERED fold (per-slot wave folds in lane 63, then the pieces in
+//   element order): the C-ABI scan's early aggregate without assuming a
+//   commutative operator.  Tile 0 has no aggregate state (it publishes its
+//   inclusive value at once) and a partial tile publishes nothing, so no
+//   other tile publishes an aggregate: the second LB_AGG publication in
+//   wave 0's code, after the chunk scans, never runs (see the note there and
+//   DESIGN.md, "Template scan").
+//   Combine: wave 0 hands the look-back's prefix over in LDS and every
+//   thread folds it into its slots' piece prefixes, instead of wave 0
+//   rewriting the NP piece prefixes before the barrier the other waves wait
+//   on.  A full tile whose every piece has a prefix (a tile after the first,
+//   or one with a left carry) in a plain inclusive scan without a right
+//   carry takes a block-uniform fast branch: op(prefix, x) per element, no
+//   per-element "has a prefix" / carry selects.
+//   Epochs: no status reset per call.  Every status word carries the
+//   launch's epoch (tag = epoch << 2 | status, a word of another epoch reads
+//   as LB_NONE) and the tile counter is reset by the block that claims the
+//   last tile, so a call is one launch; the per-segment status buffer
+//   (runtime.hpp lb_status_pool) is cleared only on (re)allocation, layout
+//   switches and epoch wrap.
 //   Status hand-off: T of <= 12 bytes is published as one self-validating
 //   8-B word per 32 bits of T, {word, status}, each an 8-B agent-scope
 //   atomic store / load (single-copy atomic; MI355X_MICROARCH "Valid forms"
@@ -48,75 +74,9 @@ namespace shp::detail {
 
 constexpr int kLbThreads = 256;
 constexpr int kLbWaves = kLbThreads / 64;
-#ifndef DR_SHP_LB_SLOTS
-#define DR_SHP_LB_SLOTS 32
-#endif
-constexpr int kLbSlots = DR_SHP_LB_SLOTS; // max U: slots per thread (wave 0 scans the U x 4 piece totals in chunks of 64)
-// VGPRs budgeted for a thread's tile + lane prefixes (lb_slots)
-#ifndef DR_SHP_LB_BUDGET
-#define DR_SHP_LB_BUDGET 160
-#endif
+constexpr int kLbSlots = 32;   // max U: slots per thread (wave 0 scans the U x 4 piece totals in chunks of 64)
+constexpr int kLbBudget = 160; // VGPRs budgeted for a thread's tile + lane prefixes (lb_slots)
 constexpr unsigned kLbSpinLimit = 1u << 22;
-// DR_SHP_LB_BUF: full aligned tiles loaded with buffer loads, the slot
-// offset in the SGPR soffset (one voffset VGPR for all U slots; a global
-// load needs a 64-bit address per slot, u * 4 KiB exceeding the 13-bit
-// immediate) -- the C-ABI scan's load (csrc/scan_kernel.hpp scan_load).
-// Round 5, lambda-op scan of 2^29 f32 (tests/cpp/bin/dense_bench, three
-// interleaved rounds on one box, profiles/r05_template_scan_ab.txt): global
-// loads 0.692 / 0.694 / 0.701 of HBM, buffer loads 0.711 / 0.725 / 0.731,
-// + early publication 0.714 / 0.726 / 0.733, + the fast combine 0.718 /
-// 0.736 / 0.718 (the fast combine alone 0.703 / 0.718 / 0.716).
-#ifndef DR_SHP_LB_BUF
-#define DR_SHP_LB_BUF 1
-#endif
-// DR_SHP_LB_PUB: wave 0 publishes the tile aggregate as soon as the chunk
-// scans have produced it, before the piece prefixes go to LDS.
-#ifndef DR_SHP_LB_PUB
-#define DR_SHP_LB_PUB 1
-#endif
-// DR_SHP_LB_FAST: the combine of a tile whose every piece has a prefix (a
-// tile after the first, or one with a left carry) in a plain inclusive scan
-// without a right carry: op(prefix, x) per element, no per-element
-// "has a prefix" / carry selects (block-uniform branch).
-#ifndef DR_SHP_LB_FAST
-#define DR_SHP_LB_FAST 1
-#endif
-// DR_SHP_LB_EARLY: the tile aggregate as an ORDERED fold (per-slot wave
-// folds in lane 63, then the pieces in element order), published before
-// the per-slot wave scans -- the C-ABI scan's early aggregate without
-// assuming a commutative operator (full tiles after the first).  Round 5,
-// lambda-op scan of 2^29 f32, three interleaved rounds on one box
-// (profiles/r05_template_scan_ab.txt): 0.720 / 0.709 / 0.719 without, 0.732
-// / 0.743 / 0.745 with; the C++ suite's non-commutative scans (affine,
-// affine3, mat2, keep-right) bit-exact with it.
-#ifndef DR_SHP_LB_EARLY
-#define DR_SHP_LB_EARLY 1
-#endif
-// DR_SHP_LB_EPOCH: no status reset per call.  Every status word carries the
-// launch's epoch (tag = epoch << 2 | status, a word of another epoch reads
-// as LB_NONE) and the tile counter is reset by the block that claims the
-// last tile, so a call is one launch; the per-segment status buffer
-// (runtime.hpp lb_status_pool) is cleared only on (re)allocation, layout
-// switches and epoch wrap.  Round 5 (profiles/r05_template_scan_ab.txt, A/B
-// #5 and #7): call-level 0.729-0.749 against 0.728-0.732 on one box, 0.740-
-// 0.745 against 0.734-0.741 on another.  Its first stress runs exposed the
-// stream-ordered pool's zero pages (profiles/r05_pool_stress.txt); on
-// hipMalloc'd memory it ran 0 failures in 110 suite runs.
-#ifndef DR_SHP_LB_EPOCH
-#define DR_SHP_LB_EPOCH 1
-#endif
-// DR_SHP_LB_TEXC: wave 0 hands the look-back's prefix over in LDS and every
-// thread folds it into its slots' piece prefixes in the combine, instead of
-// wave 0 rewriting the NP piece prefixes before the barrier the other waves
-// wait on.
-#ifndef DR_SHP_LB_TEXC
-#define DR_SHP_LB_TEXC 1
-#endif
-// DR_SHP_LB_PRIO: wave 0 runs the piece scan, look-back and publication at
-// raised issue priority (s_setprio 3): the other waves of the tile wait on it.
-#ifndef DR_SHP_LB_PRIO
-#define DR_SHP_LB_PRIO 0
-#endif
 
 enum : unsigned { LB_NONE = 0, LB_AGG = 1, LB_INCL = 2 };
 
@@ -223,7 +183,7 @@ template <typename T> struct lb_status {
   T *agg = nullptr;
   T *incl = nullptr;
   unsigned *stat = nullptr;
-  unsigned epoch = 0; // tag = epoch << 2 | status (DR_SHP_LB_EPOCH; 0 after a reset)
+  unsigned epoch = 0; // tag = epoch << 2 | status (0 after a reset)
 
   __device__ __forceinline__ unsigned decode(unsigned tag) const { return (tag >> 2) == epoch ? (tag & 3u) : LB_NONE; }
 
@@ -340,13 +300,13 @@ __device__ bool lb_lookback(const lb_status<T> &g, long tile, int lane, const Op
 }
 
 // Slots per thread: the tile (U x V values) plus one lane prefix per slot
-// kept near DR_SHP_LB_BUDGET VGPRs whatever the size of T (4-byte T: U = 32,
+// kept near kLbBudget VGPRs whatever the size of T (4-byte T: U = 32,
 // 32 K-element tiles, 2 tiles per SIMD).  Round 3 (tools/gpu_r03k.sh, lambda
 // scan of 2^29 f32): U = 32 0.768-0.789 ms against 0.828-0.835 ms for
 // U = 16 at 4 tiles per SIMD -- more bytes per look-back wait, as in the
 // C-ABI scan.
 template <typename T, int V> constexpr int lb_slots() {
-  constexpr int u = DR_SHP_LB_BUDGET / (lb_words<T> * (V + 1));
+  constexpr int u = kLbBudget / (lb_words<T> * (V + 1));
   return u < 2 ? 2 : u > kLbSlots ? kLbSlots : u;
 }
 template <typename T, int V, int U> constexpr int lb_min_waves() {
@@ -365,9 +325,9 @@ __global__ __launch_bounds__(kLbThreads, (lb_min_waves<T, V, U>())) void lb_scan
   __shared__ __attribute__((aligned(16))) unsigned char s_tot_raw[sizeof(T)];
   __shared__ bool s_has[NP];
   __shared__ bool s_fast;
-  __shared__ bool s_th;                                    // DR_SHP_LB_TEXC: the tile has a prefix
+  __shared__ bool s_th;                                    // the tile has a prefix (from the look-back or the left carry)
   __shared__ __attribute__((aligned(16))) unsigned char s_tex_raw[sizeof(T)]; // ... and its value
-  __shared__ __attribute__((aligned(16))) unsigned char s_er_raw[(DR_SHP_LB_EARLY ? NP : 1) * sizeof(T)];
+  __shared__ __attribute__((aligned(16))) unsigned char s_er_raw[NP * sizeof(T)]; // early aggregate: per-slot wave folds
   __shared__ unsigned s_tile;
   T *s_wt = reinterpret_cast<T *>(s_wt_raw);
   T *s_pre = reinterpret_cast<T *>(s_pre_raw);
@@ -375,10 +335,10 @@ __global__ __launch_bounds__(kLbThreads, (lb_min_waves<T, V, U>())) void lb_scan
   const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
   if (tid == 0) {
     const unsigned t = atomicAdd(a.counter, 1u);
-    // DR_SHP_LB_EPOCH: the last claim resets the counter for the next call
-    // (every other block has claimed already; the next call on this stream
-    // starts after this grid)
-    if (DR_SHP_LB_EPOCH && t == gridDim.x - 1)
+    // the last claim resets the counter for the next call (every other
+    // block has claimed already; the next call on this stream starts after
+    // this grid)
+    if (t == gridDim.x - 1)
       __hip_atomic_store(a.counter, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     s_tile = t;
   }
@@ -398,7 +358,7 @@ __global__ __launch_bounds__(kLbThreads, (lb_min_waves<T, V, U>())) void lb_scan
   if constexpr (VEC) {
     typedef unsigned v4u __attribute__((ext_vector_type(4)));
     const T *src = in + base;
-    if (full && DR_SHP_LB_BUF) {
+    if (full) {
       const std::uint64_t ad = reinterpret_cast<std::uint64_t>(src);
       const std::uint32_t lo = __builtin_amdgcn_readfirstlane(static_cast<std::uint32_t>(ad));
       const std::uint32_t hi = __builtin_amdgcn_readfirstlane(static_cast<std::uint32_t>(ad >> 32));
@@ -408,13 +368,6 @@ __global__ __launch_bounds__(kLbThreads, (lb_min_waves<T, V, U>())) void lb_scan
 #pragma unroll
       for (int u = 0; u < U; u++) {
         const v4u w = __builtin_amdgcn_raw_buffer_load_b128(rs, tid * 16, u * NT * 16, 2 /* nt */);
-        __builtin_memcpy(&v[u][0], &w, 16);
-      }
-    } else if (full) {
-      const v4u *p = reinterpret_cast<const v4u *>(src);
-#pragma unroll
-      for (int u = 0; u < U; u++) {
-        const v4u w = __builtin_nontemporal_load(p + u * NT + tid);
         __builtin_memcpy(&v[u][0], &w, 16);
       }
     } else {
@@ -439,33 +392,30 @@ __global__ __launch_bounds__(kLbThreads, (lb_min_waves<T, V, U>())) void lb_scan
   for (int u = 0; u < U; u++)
 #pragma unroll
     for (int j = 1; j < V; j++) v[u][j] = static_cast<T>(op(v[u][j - 1], v[u][j]));
-  // ---- early aggregate (DR_SHP_LB_EARLY): ordered, published by wave 0
-  //      before the wave scans below
-  constexpr bool EARLY = DR_SHP_LB_EARLY;
-  const bool early = EARLY && full && tile != 0; // block-uniform
+  // ---- early aggregate: ordered, published by wave 0 before the wave scans
+  //      below
+  const bool early = full && tile != 0; // block-uniform
   T eagg{};
-  if constexpr (EARLY) {
-    if (early) {
-      T *s_er = reinterpret_cast<T *>(s_er_raw);
+  if (early) {
+    T *s_er = reinterpret_cast<T *>(s_er_raw);
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        const T r = lb_wave_fold_last(v[u][V - 1], op);
-        if (lane == 63) s_er[u * NW + wid] = r;
-      }
-      __syncthreads();
-      if (wid == 0) {
+    for (int u = 0; u < U; u++) {
+      const T r = lb_wave_fold_last(v[u][V - 1], op);
+      if (lane == 63) s_er[u * NW + wid] = r;
+    }
+    __syncthreads();
+    if (wid == 0) {
 #pragma unroll
-        for (int c0 = 0; c0 < NP; c0 += 64) {
-          // a partial last chunk (NP not a multiple of 64): the masked scan,
-          // read at its last valid lane
-          const int cnt = NP - c0 < 64 ? NP - c0 : 64;
-          const T pt = s_er[c0 + lane < NP ? c0 + lane : NP - 1];
-          const T ct = cnt == 64 ? lb_readlane(lb_wave_fold_last(pt, op), 63)
-                                 : lb_readlane(lb_wave_scan(pt, op, lane), cnt - 1);
-          eagg = c0 == 0 ? ct : static_cast<T>(op(eagg, ct));
-        }
-        if (lane == 0) a.status.publish(tile, LB_AGG, eagg);
+      for (int c0 = 0; c0 < NP; c0 += 64) {
+        // a partial last chunk (NP not a multiple of 64): the masked scan,
+        // read at its last valid lane
+        const int cnt = NP - c0 < 64 ? NP - c0 : 64;
+        const T pt = s_er[c0 + lane < NP ? c0 + lane : NP - 1];
+        const T ct = cnt == 64 ? lb_readlane(lb_wave_fold_last(pt, op), 63)
+                               : lb_readlane(lb_wave_scan(pt, op, lane), cnt - 1);
+        eagg = c0 == 0 ? ct : static_cast<T>(op(eagg, ct));
       }
+      if (lane == 0) a.status.publish(tile, LB_AGG, eagg);
     }
   }
   T lx[U]; // becomes the lane's exclusive prefix inside its wave (lane 0: none)
@@ -480,54 +430,39 @@ __global__ __launch_bounds__(kLbThreads, (lb_min_waves<T, V, U>())) void lb_scan
   // ---- wave 0: piece prefixes (in chunks of 64 pieces), tile aggregate,
   //      look-back, publication
   if (wid == 0) {
-    if constexpr (DR_SHP_LB_PRIO) __builtin_amdgcn_s_setprio(3);
     T agg{};
     bool ah = false; // agg holds the fold of the chunks so far
     constexpr int NC = (NP + 63) / 64;
-    T pins[NC], aggs[NC]; // DR_SHP_LB_PUB: each chunk's scan and the fold before it
+    T pins[NC], aggs[NC]; // each chunk's scan and the fold of the chunks before it
 #pragma unroll
     for (int c = 0; c < NC; c++) {
       const int c0 = c * 64, idx = c0 + lane;
       const T pt = s_wt[idx < NP ? idx : NP - 1];
       const T pin = lb_wave_scan(pt, op, lane);
-      if constexpr (DR_SHP_LB_PUB) {
-        pins[c] = pin;
-        aggs[c] = agg;
-      } else {
-        const T pex = lb_dpp<0x138, 0xf>(pin, pin); // lane l > 0: this chunk's pieces before l
-        T p = pex;
-        bool ph = lane > 0;
-        if (ah) {
-          p = ph ? static_cast<T>(op(agg, pex)) : agg;
-          ph = true;
-        }
-        if (idx < NP) {
-          s_pre[idx] = p;
-          s_has[idx] = ph;
-        }
-      }
+      pins[c] = pin;
+      aggs[c] = agg;
       const T ctot = lb_readlane(pin, (NP - c0 < 64 ? NP - c0 : 64) - 1);
       agg = ah ? static_cast<T>(op(agg, ctot)) : ctot;
       ah = true;
     }
     if (early) agg = eagg; // the value already published
-    if constexpr (DR_SHP_LB_PUB)
-      if (!early && tile != 0 && full && lane == 0) a.status.publish(tile, LB_AGG, agg);
-    if constexpr (DR_SHP_LB_PUB) {
+    // never true (early covers every full tile after the first), but the
+    // compiler schedules wave 0's code differently without it: removing it
+    // is a change to measure, not a clean-up
+    if (!early && tile != 0 && full && lane == 0) a.status.publish(tile, LB_AGG, agg);
 #pragma unroll
-      for (int c = 0; c < NC; c++) {
-        const int idx = c * 64 + lane;
-        const T pex = lb_dpp<0x138, 0xf>(pins[c], pins[c]);
-        T p = pex;
-        bool ph = lane > 0;
-        if (c > 0) {
-          p = ph ? static_cast<T>(op(aggs[c], pex)) : aggs[c];
-          ph = true;
-        }
-        if (idx < NP) {
-          s_pre[idx] = p;
-          s_has[idx] = ph;
-        }
+    for (int c = 0; c < NC; c++) {
+      const int idx = c * 64 + lane;
+      const T pex = lb_dpp<0x138, 0xf>(pins[c], pins[c]); // lane l > 0: this chunk's pieces before l
+      T p = pex;
+      bool ph = lane > 0;
+      if (c > 0) {
+        p = ph ? static_cast<T>(op(aggs[c], pex)) : aggs[c];
+        ph = true;
+      }
+      if (idx < NP) {
+        s_pre[idx] = p;
+        s_has[idx] = ph;
       }
     }
     T tex{};
@@ -539,54 +474,42 @@ __global__ __launch_bounds__(kLbThreads, (lb_min_waves<T, V, U>())) void lb_scan
       }
       if (full && lane == 0) a.status.publish(0, LB_INCL, th ? static_cast<T>(op(tex, agg)) : agg);
     } else {
-      if (!DR_SHP_LB_PUB && !early && full && lane == 0) a.status.publish(tile, LB_AGG, agg);
       th = lb_lookback(a.status, static_cast<long>(tile), lane, op, tex, a.err);
       if (full && lane == 0) a.status.publish(tile, LB_INCL, th ? static_cast<T>(op(tex, agg)) : agg);
     }
-    if (DR_SHP_LB_TEXC) {
-      if (lane == 0) {
-        s_th = th;
-        *reinterpret_cast<T *>(s_tex_raw) = tex;
-      }
-    } else if (th) {
-#pragma unroll
-      for (int c0 = 0; c0 < NP; c0 += 64) {
-        const int idx = c0 + lane;
-        if (idx < NP) {
-          s_pre[idx] = s_has[idx] ? static_cast<T>(op(tex, s_pre[idx])) : tex;
-          s_has[idx] = true;
-        }
-      }
+    // the tile's prefix goes to LDS; every thread folds it into its slots'
+    // piece prefixes in the combine
+    if (lane == 0) {
+      s_th = th;
+      *reinterpret_cast<T *>(s_tex_raw) = tex;
     }
     if (full && tile == ntiles - 1 && lane == 0 && a.total) *a.total = th ? static_cast<T>(op(tex, agg)) : agg;
-    if (lane == 0) s_fast = DR_SHP_LB_FAST && th && full && !a.exclusive && !a.has_r && !a.reduce_only;
-    if constexpr (DR_SHP_LB_PRIO) __builtin_amdgcn_s_setprio(0);
+    if (lane == 0) s_fast = th && full && !a.exclusive && !a.has_r && !a.reduce_only;
   }
   __syncthreads();
-  if constexpr (DR_SHP_LB_FAST) {
-    if (s_fast) {
-      // every piece has a prefix: s_pre[p] = fold of everything before piece
-      // p; lane l > 0 adds its wave-exclusive prefix lx
-      const T tx = *reinterpret_cast<const T *>(s_tex_raw);
+  if (s_fast) {
+    // every piece has a prefix: op(tile prefix, s_pre[p]) = fold of
+    // everything before piece p (the tile prefix alone for the tile's first
+    // piece); lane l > 0 adds its wave-exclusive prefix lx
+    const T tx = *reinterpret_cast<const T *>(s_tex_raw);
 #pragma unroll
-      for (int u = 0; u < U; u++) {
-        T sp = s_pre[u * NW + wid];
-        if constexpr (DR_SHP_LB_TEXC) sp = s_has[u * NW + wid] ? static_cast<T>(op(tx, sp)) : tx;
-        const T pp = lane > 0 ? static_cast<T>(op(sp, lx[u])) : sp;
-        T r[V];
+    for (int u = 0; u < U; u++) {
+      T sp = s_pre[u * NW + wid];
+      sp = s_has[u * NW + wid] ? static_cast<T>(op(tx, sp)) : tx;
+      const T pp = lane > 0 ? static_cast<T>(op(sp, lx[u])) : sp;
+      T r[V];
 #pragma unroll
-        for (int j = 0; j < V; j++) r[j] = static_cast<T>(op(pp, v[u][j]));
-        if constexpr (VEC) {
-          typedef unsigned v4u __attribute__((ext_vector_type(4)));
-          v4u w;
-          __builtin_memcpy(&w, r, 16);
-          __builtin_nontemporal_store(w, reinterpret_cast<v4u *>(out + base) + u * NT + tid);
-        } else {
-          out(base + (std::size_t)u * NT + tid) = r[0];
-        }
+      for (int j = 0; j < V; j++) r[j] = static_cast<T>(op(pp, v[u][j]));
+      if constexpr (VEC) {
+        typedef unsigned v4u __attribute__((ext_vector_type(4)));
+        v4u w;
+        __builtin_memcpy(&w, r, 16);
+        __builtin_nontemporal_store(w, reinterpret_cast<v4u *>(out + base) + u * NT + tid);
+      } else {
+        out(base + (std::size_t)u * NT + tid) = r[0];
       }
-      return;
     }
+    return;
   }
 
   // ---- combine (and store)
@@ -595,7 +518,7 @@ __global__ __launch_bounds__(kLbThreads, (lb_min_waves<T, V, U>())) void lb_scan
   for (int u = 0; u < U; u++) {
     T sp = s_pre[u * NW + wid];
     bool sh = s_has[u * NW + wid];
-    if (DR_SHP_LB_TEXC && s_th) {
+    if (s_th) {
       sp = sh ? static_cast<T>(op(*reinterpret_cast<const T *>(s_tex_raw), sp)) : *reinterpret_cast<const T *>(s_tex_raw);
       sh = true;
     }
@@ -673,14 +596,8 @@ void lb_scan_launch(const SI &in, const SO &out, Op op, bool has_l, T lcarry, bo
     const std::size_t val_bytes = lb_small<T> ? 0 : 2 * ntiles * ((sizeof(T) + 15) & ~std::size_t(15));
     // the value arrays start at the next 256-B boundary after the status words
     const std::size_t span = head + ((stat_bytes + 255) & ~std::size_t(255)) + val_bytes;
-    char *ws = nullptr;
     unsigned epoch = 0;
-    if constexpr (DR_SHP_LB_EPOCH) {
-      ws = static_cast<char *>(lb_status_buffers().get(rank, span, head + stat_bytes,
-                                                      !lb_small<T>, st, epoch));
-    } else {
-      ws = static_cast<char *>(device_scratch().get(rank, span));
-    }
+    char *ws = static_cast<char *>(lb_status_buffers().get(rank, span, head + stat_bytes, !lb_small<T>, st, epoch));
     lb_args<T> a{};
     a.status.epoch = epoch;
     a.counter = reinterpret_cast<unsigned *>(ws);
@@ -700,7 +617,6 @@ void lb_scan_launch(const SI &in, const SO &out, Op op, bool has_l, T lcarry, bo
     a.reduce_only = reduce_only;
     a.total = total;
     a.err = err;
-    if constexpr (!DR_SHP_LB_EPOCH) hip_check(hipMemsetAsync(ws, 0, head + stat_bytes, st), "scan status reset");
     hipLaunchKernelGGL((lb_scan_kernel<T, V, U, VEC, decltype(in_acc), decltype(out_acc), Op>),
                        dim3(static_cast<unsigned>(ntiles)), dim3(kLbThreads), 0, st, in_acc, out_acc, n, op, a);
     hip_check(hipGetLastError(), "look-back scan launch");

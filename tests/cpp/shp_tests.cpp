@@ -1191,10 +1191,11 @@ TEST(ShpExtra, ScanNonCommutative) {
 }
 
 TEST(ShpExtra, ScanStatusLayoutSwitch) {
-  // Under DR_SHP_LB_EPOCH (a build knob, off by default) the template scan
-  // keeps its status words between calls (epoch tags, dr/shp/runtime.hpp
-  // lb_status_pool); without it this is a plain small / large / small
-  // element-size alternation.  A small-T scan publishes {value,
+  // The template scan never resets its status words per call: every word
+  // carries the call's epoch tag and the buffer is kept between calls
+  // (dr/shp/scan.hpp "Epochs", dr/shp/runtime.hpp lb_status_pool), cleared
+  // only on allocation, layout switch and epoch wrap.  This test is about
+  // the layout switch.  A small-T scan publishes {value,
   // tag} words exactly where a following large-T (mat2) scan reads its tag
   // words, so here the int scan's tile values are set to the tag the mat2
   // scan would carry if the buffer were not cleared on the layout switch

@@ -105,8 +105,9 @@ def test_sort_patterns(dr, oracle, algo, dtype, kind, n):
 def test_sort_skewed_digits(dr, oracle, algo, dtype, kind, n):
     """Keys whose high digits are constant (small integers) or all digits
     (one value): whole waves take the one-update fast paths of the ranking
-    and of the pre-pass counts (sort.hip kSortUniFast), full and partial
-    tiles mixed; bit-exact against the oracle."""
+    and of the pre-pass counts (the one-digit tests of sort.hip
+    rank_keys_atomic / radix_tile_hist0), full and partial tiles mixed;
+    bit-exact against the oracle."""
     x = make_keys(dtype, n, kind, 17)
     assert np.array_equal(run_sort(dr, x).view(np.uint8), oracle.sort(x).view(np.uint8))
 
