@@ -132,6 +132,11 @@ template <> struct KeyBits<DRHIP_F64> {
   }
 };
 
+// payload of the by-key sort: values move as bits beside their keys
+// (uint32_t or uint64_t); NoVal = keys only, every payload step compiles away
+struct NoVal {};
+template <typename V> constexpr bool kHasVal = !std::is_same_v<V, NoVal>;
+
 // ---------------------------------------------------------------- hist
 template <int DT, bool XIN, bool BIG>
 __global__ __launch_bounds__(kSortThreads) void radix_hist(const typename KeyBits<DT>::U *keys, size_t n,
@@ -365,11 +370,44 @@ __device__ __forceinline__ void load_subtile(typename KeyBits<DT>::U (&key)[KPL]
   }
 }
 
+// the payload forms (by-key sort): a sub-tile's values load with the keys'
+// li indexing, and every value goes to the LDS slot its key gets
+template <typename V, int KPL, int KPW>
+__device__ __forceinline__ void load_subtile_vals(V (&val)[KPL], const V *vsrc, size_t sb, unsigned vld, int lane,
+                                                  int wid) {
+#pragma unroll
+  for (int r = 0; r < KPL; r++) {
+    const unsigned li = wid * KPW + r * kWave + lane;
+    val[r] = li < vld ? __builtin_nontemporal_load(vsrc + sb + li) : V(0);
+  }
+}
+
+template <typename U, typename V, int SUB, int KPL, int KPW, int NW = kSortWaves>
+__device__ __forceinline__ void reorder_pairs(RankSmem<U, SUB, NW> &sm, V *s_val, const U (&key)[KPL],
+                                              const V (&val)[KPL], const uint32_t (&rank2)[(KPL + 1) / 2],
+                                              unsigned valid, int shift, int lane, int wid) {
+#pragma unroll
+  for (int r = 0; r < KPL; r++) {
+    const unsigned li = wid * KPW + r * kWave + lane;
+    const unsigned d = li < valid ? (unsigned)(key[r] >> shift) & 0xFF : (unsigned)kRadix;
+    const uint32_t rk = (r & 1) ? rank2[r / 2] >> 16 : rank2[r / 2] & 0xFFFFu;
+    const uint32_t slot = sm.wcnt[wid][d] + rk;
+    sm.keys[slot] = key[r];
+    s_val[slot] = val[r];
+  }
+}
+
 // -------------------------------------------------------------- scatter
-template <int DT, bool XIN, bool XOUT, bool BIG, bool AR>
+// V = NoVal: keys only.  V = uint32_t / uint64_t (drhip_sort_pairs): the
+// values ride along -- loaded beside the keys, reordered into a second LDS
+// array by their keys' slots, stored beside the keys.  Pairs always take the
+// small block shape (4-byte keys with 8-byte values: 16 + 32 KiB of keys and
+// values + 5 KiB of counters; the 64 K-key shape would pass 64 KiB).
+template <int DT, bool XIN, bool XOUT, bool BIG, bool AR, typename V = NoVal>
 __global__ __launch_bounds__(kSortThreads, (SortCfg<typename KeyBits<DT>::U, BIG>::MINW)) void radix_scatter(
     const typename KeyBits<DT>::U *src, typename KeyBits<DT>::U *dst, size_t n, int shift, const uint32_t *hist,
-    const uint32_t *off, unsigned nblocks) {
+    const uint32_t *off, unsigned nblocks, const V *vsrc, V *vdst) {
+  static_assert(!(BIG && kHasVal<V>), "pairs use the small block shape");
   using U = typename KeyBits<DT>::U;
   using Cfg = SortCfg<U, BIG>;
   constexpr int kSubTiles = Cfg::SUBTILES;
@@ -380,6 +418,11 @@ __global__ __launch_bounds__(kSortThreads, (SortCfg<typename KeyBits<DT>::U, BIG
   __shared__ RankSmem<U, SUB> sm;
   __shared__ uint32_t s_run[kRadix]; // global write cursor per digit
   __shared__ uint32_t s_cur[kRadix]; // s_run - the digit's start in the sub-tile
+  V *s_val = nullptr;                // the values of sm.keys, slot for slot
+  if constexpr (kHasVal<V>) {
+    __shared__ V s_val_arr[SUB];
+    s_val = s_val_arr;
+  }
 
   const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave;
   const size_t base = (size_t)blockIdx.x * Cfg::CH;
@@ -393,25 +436,32 @@ __global__ __launch_bounds__(kSortThreads, (SortCfg<typename KeyBits<DT>::U, BIG
   // The next sub-tile is loaded as soon as this one's keys are in LDS, so its
   // latency hides under the write-out phase.
   U key[KPL];
+  std::conditional_t<kHasVal<V>, V, char> val[kHasVal<V> ? KPL : 1];
+  (void)val;
   auto valid_at = [&](size_t sb) -> unsigned {
     return sb < n ? (unsigned)(n - sb < (size_t)SUB ? n - sb : (size_t)SUB) : 0u;
   };
   size_t sbase = base;
   unsigned valid = valid_at(sbase);
   if (valid) load_subtile<DT, XIN, KPL, KPW>(key, src, sbase, valid, lane, wid);
+  if constexpr (kHasVal<V>)
+    if (valid) load_subtile_vals<V, KPL, KPW>(val, vsrc, sbase, valid, lane, wid);
   for (int st = 0; st < kSubTiles; st++) {
     if (!valid) break; // uniform
     uint32_t rank2[(KPL + 1) / 2]; // two 16-bit ranks per register (no spills at 4 waves/SIMD)
     rank_subtile<AR, U, KPL, KPW>(key, rank2, valid, (unsigned)SUB, shift, sm.wcnt[wid], lane, wid);
     __syncthreads();
     digit_offsets(sm, tid);
-    reorder_keys<U, SUB, KPL, KPW>(sm, key, rank2, valid, shift, lane, wid);
+    if constexpr (kHasVal<V>) reorder_pairs<U, V, SUB, KPL, KPW>(sm, s_val, key, val, rank2, valid, shift, lane, wid);
+    else reorder_keys<U, SUB, KPL, KPW>(sm, key, rank2, valid, shift, lane, wid);
     // global cursor of digit d minus its start in the sub-tile: key p of the
     // reordered sub-tile goes to s_cur[d] + p
     for (int d = tid; d < kRadix; d += kSortThreads) s_cur[d] = s_run[d] - sm.start[d];
     const size_t nbase = sbase + SUB;
     const unsigned nvalid = st + 1 < kSubTiles ? valid_at(nbase) : 0u;
     if (nvalid) load_subtile<DT, XIN, KPL, KPW>(key, src, nbase, nvalid, lane, wid);
+    if constexpr (kHasVal<V>)
+      if (nvalid) load_subtile_vals<V, KPL, KPW>(val, vsrc, nbase, nvalid, lane, wid);
     __syncthreads();
     // ---- write each digit's run contiguously (valid keys occupy [0, valid))
 #pragma unroll
@@ -421,6 +471,7 @@ __global__ __launch_bounds__(kSortThreads, (SortCfg<typename KeyBits<DT>::U, BIG
         const U k = sm.keys[p];
         const unsigned d = (unsigned)(k >> shift) & 0xFF;
         dst[s_cur[d] + p] = XOUT ? KeyBits<DT>::out(k) : k;
+        if constexpr (kHasVal<V>) vdst[s_cur[d] + p] = s_val[p];
       }
     }
     __syncthreads();
@@ -1091,8 +1142,9 @@ __global__ void bucket_count_kernel(const typename KeyBits<DT>::U *sorted, size_
 // The distributed sort's destination step: after the all-to-all every rank
 // holds P sorted runs (one from each source), which pairwise merge-path
 // rounds (ceil(log2 P) passes of 8 B/key for 4-byte keys) put in order
-// instead of a second full radix sort (48 B/key).  Keys only, so ties need
-// no stability; runs of pair p are A (earlier) and B, A first on ties.
+// instead of a second full radix sort (48 B/key).  Runs of pair p are A
+// (earlier) and B, A first on ties: invisible for keys alone, and what makes
+// the payload form (merge_tiles<DT, V>, the by-key sort) stable.
 constexpr int kMergeThreads = 256;
 constexpr int kMergeIPT = 8; // outputs per thread
 constexpr int kMergeTile = kMergeThreads * kMergeIPT;
@@ -1142,10 +1194,16 @@ __global__ void merge_partition(const typename KeyBits<DT>::U *src, MergePairs m
   split[t] = merge_corank<DT>(A, m, A + m, k, d);
 }
 
-template <int DT>
+// V != NoVal (drhip_merge_pairs_runs_to): the thread that emits output q
+// knows whether it came from A at ia or from B at ib, and reads the value at
+// the matching position of the value runs straight from memory (a thread's
+// 8 outputs walk two contiguous stretches, so the reads stay within a few
+// lines); the keys' 32 KiB of LDS at 8-byte keys is all the kernel stages.
+template <int DT, typename V = NoVal>
 __global__ __launch_bounds__(kMergeThreads) void merge_tiles(const typename KeyBits<DT>::U *src,
                                                             typename KeyBits<DT>::U *dst, MergePairs mp,
-                                                            const unsigned long long *split) {
+                                                            const unsigned long long *split, const V *vsrc,
+                                                            V *vdst) {
   using U = typename KeyBits<DT>::U;
   __shared__ U s_a[kMergeTile], s_b[kMergeTile];
   const unsigned g = blockIdx.x;
@@ -1171,22 +1229,44 @@ __global__ __launch_bounds__(kMergeThreads) void merge_tiles(const typename KeyB
   }
   unsigned ia = lo, ib = od - lo;
   U out[kMergeIPT];
+  std::conditional_t<kHasVal<V>, V, char> vout[kHasVal<V> ? kMergeIPT : 1];
+  (void)vout;
 #pragma unroll
   for (int q = 0; q < kMergeIPT; q++) {
     const bool take_a = ib >= nbk || (ia < na && merge_le<DT>(s_a[ia], s_b[ib]));
     out[q] = take_a ? s_a[ia < na ? ia : 0] : s_b[ib < nbk ? ib : 0];
+    if constexpr (kHasVal<V>) {
+      // outputs past the tile's end have no source position
+      const V *vA = vsrc + mp.a0[p], *vB = vA + m;
+      if (od + q < tot) vout[q] = take_a ? vA[i0 + ia] : vB[j0 + ib];
+    }
     ia += take_a;
     ib += !take_a;
   }
   U *o = dst + mp.a0[p] + d0 + od;
   const unsigned cnt = tot - od < (unsigned)kMergeIPT ? tot - od : (unsigned)kMergeIPT;
-  if (cnt == (unsigned)kMergeIPT && ((uintptr_t)o % 16) == 0) {
-    constexpr int V = 16 / sizeof(U);
+  if constexpr (kHasVal<V>) {
+    V *vo = vdst + mp.a0[p] + d0 + od;
+    if (cnt == (unsigned)kMergeIPT && ((uintptr_t)vo % 16) == 0) {
+      constexpr int W = 16 / sizeof(V);
 #pragma unroll
-    for (int q = 0; q < kMergeIPT; q += V) {
+      for (int q = 0; q < kMergeIPT; q += W) {
+        Vec16<V> v;
+#pragma unroll
+        for (int j = 0; j < W; j++) v.v[j] = vout[q + j];
+        *reinterpret_cast<Vec16<V> *>(vo + q) = v;
+      }
+    } else {
+      for (unsigned q = 0; q < cnt; q++) vo[q] = vout[q];
+    }
+  }
+  if (cnt == (unsigned)kMergeIPT && ((uintptr_t)o % 16) == 0) {
+    constexpr int KV = 16 / sizeof(U);
+#pragma unroll
+    for (int q = 0; q < kMergeIPT; q += KV) {
       Vec16<U> v;
 #pragma unroll
-      for (int j = 0; j < V; j++) v.v[j] = out[q + j];
+      for (int j = 0; j < KV; j++) v.v[j] = out[q + j];
       *reinterpret_cast<Vec16<U> *>(o + q) = v;
     }
   } else {
@@ -1424,7 +1504,8 @@ bool sort_rank_atomic(Segment *s) {
 
 } // namespace
 
-template <int DT, bool BIG, bool AR> static int launch_sort_cfg(Segment *s, int seg, void *keys, size_t n, void *tmp);
+template <int DT, bool BIG, bool AR, typename V = NoVal>
+static int launch_sort_cfg(Segment *s, int seg, void *keys, size_t n, void *tmp, V *vals = nullptr);
 template <int DT, bool BIG, bool AR, int NT = kSortThreads>
 static int launch_onesweep(Segment *s, int seg, void *keys, size_t n, void *tmp);
 
@@ -1547,17 +1628,24 @@ static int launch_onesweep(Segment *s, int seg, void *keys, size_t n, void *tmp)
   return DRHIP_OK;
 }
 
-template <int DT, bool BIG, bool AR> static int launch_sort_cfg(Segment *s, int seg, void *keys, size_t n, void *tmp) {
+// The classic three-kernel pass.  V != NoVal (drhip_sort_pairs): the values
+// ride through radix_scatter, at the small block shape whatever n, and the
+// workspace is [alt keys | alt values | hist | off]; 4 + 8 + 8 = 20 B per
+// u32 + u32 pair and pass.
+template <int DT, bool BIG, bool AR, typename V>
+static int launch_sort_cfg(Segment *s, int seg, void *keys, size_t n, void *tmp, V *vals) {
   using U = typename KeyBits<DT>::U;
   using Cfg = SortCfg<U, BIG>;
-  const size_t nb = sort_nblocks<U>(n);
+  const size_t nb = (n + Cfg::CH - 1) / Cfg::CH;
   const size_t keys_b = (n * sizeof(U) + 255) & ~size_t(255);
+  const size_t vals_b = kHasVal<V> ? (n * sizeof(V) + 255) & ~size_t(255) : 0;
   const size_t hist_b = (nb * kRadix * 4 + 255) & ~size_t(255);
   U *alt = (U *)tmp;
-  uint32_t *hist = (uint32_t *)((char *)tmp + keys_b);
-  uint32_t *off = (uint32_t *)((char *)tmp + keys_b + hist_b);
+  uint32_t *hist = (uint32_t *)((char *)tmp + keys_b + vals_b);
+  uint32_t *off = (uint32_t *)((char *)tmp + keys_b + vals_b + hist_b);
   DRHIP_CHECK_HIP(hipSetDevice(s->device));
   U *a = (U *)keys, *b = alt;
+  V *va = vals, *vb = (V *)((char *)tmp + keys_b);
   for (int p = 0; p < Cfg::PASSES; p++) {
     const int shift = 8 * p;
     const bool first = p == 0, last = p == Cfg::PASSES - 1;
@@ -1572,20 +1660,70 @@ template <int DT, bool BIG, bool AR> static int launch_sort_cfg(Segment *s, int 
     int rc = scan_inclusive_u32(s, seg, hist, off, nb * kRadix);
     if (rc) return rc;
 #define DRHIP_SCATTER(XI, XO)                                                                          \
-  hipLaunchKernelGGL((radix_scatter<DT, XI, XO, BIG, AR>), dim3((unsigned)nb), dim3(kSortThreads), 0, s->stream, a, \
-                     b, n, shift, hist, off, (unsigned)nb)
-    if (first && last) DRHIP_SCATTER(true, true);
-    else if (first) DRHIP_SCATTER(true, false);
+  hipLaunchKernelGGL((radix_scatter<DT, XI, XO, BIG, AR, V>), dim3((unsigned)nb), dim3(kSortThreads), 0, s->stream, \
+                     a, b, n, shift, hist, off, (unsigned)nb, (const V *)va, vb)
+    if (first && last) {
+      if constexpr (!kHasVal<V>) DRHIP_SCATTER(true, true); // pairs: 4 or 8 passes, never one
+    } else if (first) DRHIP_SCATTER(true, false);
     else if (last) DRHIP_SCATTER(false, true);
     else DRHIP_SCATTER(false, false);
 #undef DRHIP_SCATTER
     DRHIP_CHECK_LAUNCH();
-    U *t = a;
-    a = b;
-    b = t;
+    std::swap(a, b);
+    std::swap(va, vb);
   }
-  // an even number of passes leaves the result in `keys`
+  // an even number of passes leaves the result in `keys` (and `vals`)
   return DRHIP_OK;
+}
+
+// ---- by-key sort (drhip_sort_pairs): launch_sort_cfg with a payload.
+// Workspace: [alt keys | alt values | hist | off (| room up to the keys-only
+// workspace)].
+namespace {
+template <typename U> size_t pairs_nblocks(size_t n) { return (n + SortCfg<U, false>::CH - 1) / SortCfg<U, false>::CH; }
+template <typename U> size_t pairs_hist_bytes(size_t n) { return (pairs_nblocks<U>(n) * kRadix * 4 + 255) & ~size_t(255); }
+size_t pairs_vals_bytes(size_t n, size_t val_bytes) { return (n * val_bytes + 255) & ~size_t(255); }
+// never below the keys-only workspace plus the alternate values
+template <typename U> size_t sort_pairs_ws_bytes(size_t n, size_t val_bytes) {
+  const size_t keys_b = (n * sizeof(U) + 255) & ~size_t(255);
+  const size_t os_b = os_ctrl_bytes<U>() + os_status_bytes<U>(n);
+  const size_t hist2 = 2 * pairs_hist_bytes<U>(n);
+  return keys_b + pairs_vals_bytes(n, val_bytes) + (hist2 > os_b ? hist2 : os_b);
+}
+bool val_bytes_ok(size_t val_bytes) { return val_bytes == 4 || val_bytes == 8; }
+} // namespace
+
+extern "C" int drhip_sort_pairs_workspace(int seg, int kdtype, size_t val_bytes, size_t n, size_t *bytes) {
+  if (!bytes) return set_error(DRHIP_ERR_BAD_ARG, "drhip_sort_pairs_workspace: null");
+  const size_t ks = dtype_size(kdtype);
+  if (!ks || (ks != 4 && ks != 8)) return set_error(DRHIP_ERR_BAD_ARG, "sort_pairs: unsupported key dtype");
+  if (!val_bytes_ok(val_bytes)) return set_error(DRHIP_ERR_BAD_ARG, "sort_pairs: values must be 4 or 8 bytes");
+  *bytes = ks == 4 ? sort_pairs_ws_bytes<uint32_t>(n, val_bytes) : sort_pairs_ws_bytes<uint64_t>(n, val_bytes);
+  return DRHIP_OK;
+}
+
+extern "C" int drhip_sort_pairs(int seg, int kdtype, void *keys, void *vals, size_t val_bytes, size_t n, void *tmp,
+                                size_t tmp_bytes) {
+  DRHIP_GET_SEG(s, seg);
+  if (!val_bytes_ok(val_bytes)) return set_error(DRHIP_ERR_BAD_ARG, "drhip_sort_pairs: values must be 4 or 8 bytes");
+  return dispatch_sort_dtype(kdtype, [&](auto dv) -> int {
+    constexpr int DT = decltype(dv)::value;
+    using U = typename KeyBits<DT>::U;
+    if (n <= 1) return DRHIP_OK;
+    if (!keys || !vals || !tmp) return set_error(DRHIP_ERR_BAD_ARG, "drhip_sort_pairs: null pointer");
+    if (n >= (size_t(1) << 32)) return set_error(DRHIP_ERR_BAD_ARG, "sort_pairs: segment must hold < 2^32 pairs");
+    if (((uintptr_t)keys % sizeof(U)) || ((uintptr_t)vals % val_bytes) || ((uintptr_t)tmp & 255))
+      return set_error(DRHIP_ERR_BAD_ARG, "sort_pairs: keys key-aligned, vals value-aligned, tmp 256-byte aligned");
+    if (tmp_bytes < sort_pairs_ws_bytes<U>(n, val_bytes))
+      return set_error(DRHIP_ERR_BAD_ARG, "sort_pairs: workspace too small");
+    DRHIP_CHECK_HIP(hipSetDevice(s->device));
+    const bool ar = sort_rank_atomic(s);
+    if (val_bytes == 4)
+      return ar ? launch_sort_cfg<DT, false, true>(s, seg, keys, n, tmp, (uint32_t *)vals)
+                : launch_sort_cfg<DT, false, false>(s, seg, keys, n, tmp, (uint32_t *)vals);
+    return ar ? launch_sort_cfg<DT, false, true>(s, seg, keys, n, tmp, (uint64_t *)vals)
+              : launch_sort_cfg<DT, false, false>(s, seg, keys, n, tmp, (uint64_t *)vals);
+  });
 }
 
 #ifdef DRHIP_SORT_STAMPS
@@ -1671,26 +1809,40 @@ namespace {
 // the rounds alternate so that the LAST one writes dst (the first reads
 // src): no copy at all -- the distributed sort's all_to_all lands in src
 // and the merge writes straight into the segment.
-template <int DT>
+// With a payload (V != NoVal, drhip_merge_pairs_runs_to) the values take the
+// same route beside the keys: tmp = [keys | values | splits], and every
+// copy of keys is a copy of values too.
+template <int DT, typename V = NoVal>
 int merge_rounds(Segment *s, const void *src, void *dst, size_t n, const size_t *run_offsets, int nruns, void *tmp,
-                 size_t tmp_bytes) {
+                 size_t tmp_bytes, const V *vsrc = nullptr, V *vdst = nullptr) {
   using U = typename KeyBits<DT>::U;
-  if (tmp_bytes < merge_ws_bytes<U>(n, nruns)) return set_error(DRHIP_ERR_BAD_ARG, "merge: workspace too small");
+  constexpr size_t vsz = kHasVal<V> ? sizeof(V) : 0;
+  if (tmp_bytes < merge_ws_bytes<U>(n, nruns) + (vsz ? pairs_vals_bytes(n, vsz) : 0))
+    return set_error(DRHIP_ERR_BAD_ARG, "merge: workspace too small");
   DRHIP_CHECK_HIP(hipSetDevice(s->device));
   const bool in_place = src == dst;
   if (nruns == 1 || n <= 1) {
-    if (!in_place && n) DRHIP_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(U), hipMemcpyDeviceToDevice, s->stream));
+    if (!in_place && n) {
+      DRHIP_CHECK_HIP(hipMemcpyAsync(dst, src, n * sizeof(U), hipMemcpyDeviceToDevice, s->stream));
+      if constexpr (kHasVal<V>)
+        DRHIP_CHECK_HIP(hipMemcpyAsync(vdst, vsrc, n * vsz, hipMemcpyDeviceToDevice, s->stream));
+    }
     return DRHIP_OK;
   }
   const size_t keys_b = (n * sizeof(U) + 255) & ~size_t(255);
-  unsigned long long *split = (unsigned long long *)((char *)tmp + keys_b);
+  const size_t vals_b = vsz ? pairs_vals_bytes(n, vsz) : 0;
+  unsigned long long *split = (unsigned long long *)((char *)tmp + keys_b + vals_b);
   int rounds = 0;
   for (int r = nruns; r > 1; r = (r + 1) / 2) rounds++;
   U *bufs[2] = {(U *)dst, (U *)tmp};
+  V *vbufs[2] = {vdst, (V *)((char *)tmp + keys_b)};
   const U *a = (const U *)src;
+  const V *va = vsrc;
   std::vector<size_t> off(run_offsets, run_offsets + nruns + 1);
   for (int k = 0; off.size() > 2; k++) {
-    U *b = in_place ? bufs[(k + 1) & 1] : bufs[(rounds - 1 - k) & 1];
+    const int bi = in_place ? (k + 1) & 1 : (rounds - 1 - k) & 1;
+    U *b = bufs[bi];
+    V *vb = vbufs[bi];
     MergePairs mp{};
     std::vector<size_t> next;
     unsigned tiles = 0;
@@ -1711,13 +1863,18 @@ int merge_rounds(Segment *s, const void *src, void *dst, size_t n, const size_t 
     hipLaunchKernelGGL((merge_partition<DT>), dim3((nb + 255) / 256), dim3(256), 0, s->stream, a, mp, split);
     DRHIP_CHECK_LAUNCH();
     if (tiles) {
-      hipLaunchKernelGGL((merge_tiles<DT>), dim3(tiles), dim3(kMergeThreads), 0, s->stream, a, b, mp, split);
+      hipLaunchKernelGGL((merge_tiles<DT, V>), dim3(tiles), dim3(kMergeThreads), 0, s->stream, a, b, mp, split, va,
+                         vb);
       DRHIP_CHECK_LAUNCH();
     }
     a = b;
+    va = vb;
     off.swap(next);
   }
-  if (a != (const U *)dst) DRHIP_CHECK_HIP(hipMemcpyAsync(dst, a, n * sizeof(U), hipMemcpyDeviceToDevice, s->stream));
+  if (a != (const U *)dst) {
+    DRHIP_CHECK_HIP(hipMemcpyAsync(dst, a, n * sizeof(U), hipMemcpyDeviceToDevice, s->stream));
+    if constexpr (kHasVal<V>) DRHIP_CHECK_HIP(hipMemcpyAsync(vdst, va, n * vsz, hipMemcpyDeviceToDevice, s->stream));
+  }
   return DRHIP_OK;
 }
 
@@ -1758,5 +1915,45 @@ extern "C" int drhip_merge_runs_to(int seg, int dtype, const void *src, void *ds
     return set_error(DRHIP_ERR_BAD_ARG, "drhip_merge_runs_to: src and dst overlap");
   return dispatch_sort_dtype(dtype, [&](auto dv) -> int {
     return merge_rounds<decltype(dv)::value>(s, src, dst, n, run_offsets, nruns, tmp, tmp_bytes);
+  });
+}
+
+extern "C" int drhip_merge_pairs_workspace(int seg, int kdtype, size_t val_bytes, size_t n, int nruns, size_t *bytes) {
+  if (!bytes || nruns < 1) return set_error(DRHIP_ERR_BAD_ARG, "drhip_merge_pairs_workspace: bad argument");
+  const size_t ks = dtype_size(kdtype);
+  if (ks != 4 && ks != 8) return set_error(DRHIP_ERR_BAD_ARG, "merge_pairs: unsupported key dtype");
+  if (!val_bytes_ok(val_bytes)) return set_error(DRHIP_ERR_BAD_ARG, "merge_pairs: values must be 4 or 8 bytes");
+  *bytes = (ks == 4 ? merge_ws_bytes<uint32_t>(n, nruns) : merge_ws_bytes<uint64_t>(n, nruns)) +
+           pairs_vals_bytes(n, val_bytes);
+  return DRHIP_OK;
+}
+
+extern "C" int drhip_merge_pairs_runs_to(int seg, int kdtype, size_t val_bytes, const void *src_keys,
+                                         const void *src_vals, void *dst_keys, void *dst_vals, size_t n,
+                                         const size_t *run_offsets, int nruns, void *tmp, size_t tmp_bytes) {
+  DRHIP_GET_SEG(s, seg);
+  if (!val_bytes_ok(val_bytes))
+    return set_error(DRHIP_ERR_BAD_ARG, "drhip_merge_pairs_runs_to: values must be 4 or 8 bytes");
+  if (int rc = merge_check(nruns, run_offsets, n)) return rc;
+  if (n == 0) return DRHIP_OK;
+  const size_t ks = dtype_size(kdtype);
+  if (ks != 4 && ks != 8) return set_error(DRHIP_ERR_BAD_ARG, "merge_pairs: unsupported key dtype");
+  if (!src_keys || !src_vals || !dst_keys || !dst_vals || !tmp || ((uintptr_t)src_keys % ks) ||
+      ((uintptr_t)dst_keys % ks) || ((uintptr_t)src_vals % val_bytes) || ((uintptr_t)dst_vals % val_bytes) ||
+      ((uintptr_t)tmp & 255))
+    return set_error(DRHIP_ERR_BAD_ARG,
+                     "drhip_merge_pairs_runs_to: keys key-aligned, vals value-aligned, tmp 256-byte aligned");
+  auto overlap = [n](const void *a, const void *b, size_t es) {
+    return (const char *)a < (const char *)b + n * es && (const char *)b < (const char *)a + n * es;
+  };
+  if (overlap(src_keys, dst_keys, ks) || overlap(src_vals, dst_vals, val_bytes))
+    return set_error(DRHIP_ERR_BAD_ARG, "drhip_merge_pairs_runs_to: src and dst overlap");
+  return dispatch_sort_dtype(kdtype, [&](auto dv) -> int {
+    constexpr int DT = decltype(dv)::value;
+    if (val_bytes == 4)
+      return merge_rounds<DT, uint32_t>(s, src_keys, dst_keys, n, run_offsets, nruns, tmp, tmp_bytes,
+                                        (const uint32_t *)src_vals, (uint32_t *)dst_vals);
+    return merge_rounds<DT, uint64_t>(s, src_keys, dst_keys, n, run_offsets, nruns, tmp, tmp_bytes,
+                                      (const uint64_t *)src_vals, (uint64_t *)dst_vals);
   });
 }

@@ -53,6 +53,7 @@ EXPORTS = [
     "drhip_split_windows", "drhip_split_exact",
     "drhip_stencil1d", "drhip_stencil2d", "drhip_merge_workspace", "drhip_merge_runs",
     "drhip_merge_runs_to",
+    "drhip_sort_pairs_workspace", "drhip_sort_pairs", "drhip_merge_pairs_workspace", "drhip_merge_pairs_runs_to",
     "drhip_comm_unique_id", "drhip_comm_init_rank", "drhip_comm_init_all", "drhip_comm_destroy",
     "drhip_comm_rank", "drhip_comm_group_start", "drhip_comm_group_end", "drhip_allreduce",
     "drhip_allgather", "drhip_gather", "drhip_alltoallv", "drhip_halo_exchange",
@@ -111,6 +112,9 @@ def load():
         "drhip_merge_workspace": [i, i, sz, i, vp],
         "drhip_merge_runs": [i, i, vp, sz, vp, i, vp, sz],
         "drhip_merge_runs_to": [i, i, vp, vp, sz, vp, i, vp, sz],
+        "drhip_sort_pairs_workspace": [i, i, sz, sz, vp], "drhip_sort_pairs": [i, i, vp, vp, sz, sz, vp, sz],
+        "drhip_merge_pairs_workspace": [i, i, sz, sz, i, vp],
+        "drhip_merge_pairs_runs_to": [i, i, sz, vp, vp, vp, vp, sz, vp, i, vp, sz],
         "drhip_comm_unique_id": [vp], "drhip_comm_init_rank": [i, i, i, vp], "drhip_comm_init_all": [],
         "drhip_comm_destroy": [i], "drhip_comm_rank": [i, vp, vp], "drhip_comm_group_start": [],
         "drhip_comm_group_end": [], "drhip_allreduce": [i, i, i, vp, vp, sz], "drhip_allgather": [i, vp, vp, sz],
@@ -398,6 +402,32 @@ def sort_workspace(seg, dtype, n):
 
 def sort_async(seg, dtype, keys, n, tmp, tmp_bytes):
     check(load().drhip_sort(seg, DTYPES[np.dtype(dtype)], keys, n, tmp, tmp_bytes))
+
+
+def sort_pairs_workspace(seg, kdtype, val_bytes, n):
+    out = C.c_size_t(0)
+    check(load().drhip_sort_pairs_workspace(seg, DTYPES[np.dtype(kdtype)], val_bytes, n, C.byref(out)))
+    return out.value
+
+
+def sort_pairs_async(seg, kdtype, keys, vals, val_bytes, n, tmp, tmp_bytes):
+    """Stable sort of keys[0, n) with vals[i] (val_bytes = 4 or 8 each) carried beside keys[i]."""
+    check(load().drhip_sort_pairs(seg, DTYPES[np.dtype(kdtype)], keys, vals, val_bytes, n, tmp, tmp_bytes))
+
+
+def merge_pairs_workspace(seg, kdtype, val_bytes, n, nruns):
+    out = C.c_size_t(0)
+    check(load().drhip_merge_pairs_workspace(seg, DTYPES[np.dtype(kdtype)], val_bytes, n, nruns, C.byref(out)))
+    return out.value
+
+
+def merge_pairs_runs_to(seg, kdtype, val_bytes, src_keys, src_vals, dst_keys, dst_vals, n, run_offsets, tmp,
+                        tmp_bytes):
+    """(dst_keys, dst_vals)[0, n) = the stable merge of the sorted key runs [run_offsets[r],
+    run_offsets[r+1]) of src_keys, every key with its value from src_vals."""
+    offs = (C.c_size_t * len(run_offsets))(*[int(o) for o in run_offsets])
+    check(load().drhip_merge_pairs_runs_to(seg, DTYPES[np.dtype(kdtype)], val_bytes, src_keys, src_vals, dst_keys,
+                                           dst_vals, n, offs, len(run_offsets) - 1, tmp, tmp_bytes))
 
 
 def sort_sample(seg, dtype, sorted_ptr, n, stride, samples):

@@ -17,7 +17,8 @@
 //   4. every destination merges its P sorted runs (drhip_merge_runs) and
 //      copies them back into its segment.
 // All device scratch comes from the cached per-segment pool.  With P == 1
-// only step 1's sort runs.
+// only step 1's sort runs.  shp::sort_by_key (at the end of this file)
+// takes the same four steps with a value carried beside every key.
 #pragma once
 
 #include <cstring>
@@ -89,8 +90,10 @@ template <> struct key_bits<double> {
 // merge workspace | regular samples].  Segments that share a rank (a
 // distributed_span may list several segments of one rank) get disjoint
 // slices of that rank's ONE scratch block, sized for all of them.
+// sort_by_key adds the value exchange buffer (vbuf, after buf) and sizes ws /
+// mws by the pairs workspaces.
 struct sort_scratch {
-  void *ws = nullptr, *buf = nullptr, *mws = nullptr, *smp = nullptr;
+  void *ws = nullptr, *buf = nullptr, *vbuf = nullptr, *mws = nullptr, *smp = nullptr;
   std::size_t wsb = 0, mwsb = 0, bytes = 0;
 };
 
@@ -116,10 +119,96 @@ template <typename T> void carve_sort_scratch(sort_scratch &sc, char *base, std:
   sc.smp = base + align_up(sc.wsb) + bufb + align_up(sc.mwsb);
 }
 
+// The same for sort_by_key with values of vb bytes: [pairs radix workspace |
+// n-key exchange buffer | n-value exchange buffer | pairs merge workspace |
+// regular samples of the keys].
+template <typename T>
+sort_scratch size_pairs_scratch(std::size_t rank, std::size_t n, std::size_t P, std::size_t nsamples, std::size_t vb) {
+  const int r = static_cast<int>(rank);
+  sort_scratch sc;
+  check(drhip_sort_pairs_workspace(r, dtype_code<T>(), vb, n, &sc.wsb), "drhip_sort_pairs_workspace");
+  if (P > 1)
+    check(drhip_merge_pairs_workspace(r, dtype_code<T>(), vb, n, static_cast<int>(P), &sc.mwsb),
+          "drhip_merge_pairs_workspace");
+  const std::size_t bufb = P > 1 ? align_up(n * sizeof(T)) + align_up(n * vb) : 0;
+  const std::size_t smpb = P > 1 ? align_up(nsamples * sizeof(T)) : 0;
+  sc.bytes = align_up(sc.wsb) + bufb + align_up(sc.mwsb) + smpb;
+  return sc;
+}
+
+template <typename T> void carve_pairs_scratch(sort_scratch &sc, char *base, std::size_t n, std::size_t P, std::size_t vb) {
+  const std::size_t kbufb = P > 1 ? align_up(n * sizeof(T)) : 0, vbufb = P > 1 ? align_up(n * vb) : 0;
+  sc.ws = base;
+  sc.buf = base + align_up(sc.wsb);
+  sc.vbuf = base + align_up(sc.wsb) + kbufb;
+  sc.mws = base + align_up(sc.wsb) + kbufb + vbufb;
+  sc.smp = base + align_up(sc.wsb) + kbufb + vbufb + align_up(sc.mwsb);
+}
+
 // Regular samples per segment for the exact splitting (split.hip): a stride
 // of ceil(n / kSortSamples) keys keeps every boundary's bracket to a few
 // strides of keys per segment.
 constexpr std::size_t kSortSamples = std::size_t(1) << 16;
+
+} // namespace detail
+
+namespace detail {
+
+// Steps 1b-2 of the distributed sort, on keys alone (shared by shp::sort and
+// shp::sort_by_key): the regular samples of every locally sorted segment
+// come to the host, then the exact splitting at the segment boundaries.
+// Needs P > 1.  Returns split[s * P + k] = the number of segment s's keys that go to
+// destinations <= k; keys equal to a boundary key are given out in segment
+// order, which is what keeps sort_by_key stable across segments.
+template <typename T>
+std::vector<std::uint64_t> exact_splits(const std::vector<device_span<T>> &parts, const std::vector<sort_scratch> &sc,
+                                        const std::vector<std::uint64_t> &n, const std::vector<std::uint64_t> &stride,
+                                        const std::vector<std::uint64_t> &ns) {
+  using KB = key_bits<T>;
+  const std::size_t P = parts.size(), nb = P - 1;
+  std::size_t tot_smp = 0;
+  for (auto v : ns) tot_smp += v;
+  pinned<T> hs(tot_smp);
+  for (std::size_t k = 0, off = 0; k < P; off += ns[k], k++)
+    check(drhip_memcpy_d2h(static_cast<int>(parts[k].rank()), hs.data() + off, sc[k].smp, ns[k] * sizeof(T)),
+          "sort samples d2h");
+  for (std::size_t k = 0; k < P; k++) sync(parts[k].rank());
+
+  // 2. exact splitting at the segment boundaries (csrc/split.hip): value
+  //    brackets from the samples, then each boundary key on the slices of
+  //    every sorted segment that hold its bracket
+  std::vector<std::uint64_t> g(nb), lo(nb), hi(nb), win(2 * P * nb), split(P * (nb + 1));
+  for (std::size_t k = 0, acc = 0; k < nb; k++) g[k] = acc += n[k];
+  {
+    std::vector<std::uint64_t> bits(tot_smp);
+    for (std::size_t i = 0; i < tot_smp; i++) bits[i] = static_cast<std::uint64_t>(KB::in(hs[i]));
+    check(drhip_split_windows(static_cast<int>(P), n.data(), stride.data(), ns.data(), bits.data(),
+                              static_cast<int>(nb), g.data(), lo.data(), hi.data(), win.data()),
+          "drhip_split_windows");
+  }
+  std::size_t tot_win = 0;
+  for (std::size_t i = 0; i < P * nb; i++) tot_win += win[2 * i + 1] - win[2 * i];
+  {
+    pinned<T> hw(tot_win);
+    std::size_t off = 0;
+    for (std::size_t s = 0; s < P; s++)
+      for (std::size_t k = 0; k < nb; k++) {
+        const std::size_t a = win[2 * (s * nb + k)], b = win[2 * (s * nb + k) + 1];
+        if (b > a)
+          check(drhip_memcpy_d2h(static_cast<int>(parts[s].rank()), hw.data() + off, parts[s].data() + a,
+                                 (b - a) * sizeof(T)),
+                "sort slices d2h");
+        off += b - a;
+      }
+    for (std::size_t s = 0; s < P; s++) sync(parts[s].rank());
+    std::vector<std::uint64_t> wbits(tot_win);
+    for (std::size_t i = 0; i < tot_win; i++) wbits[i] = static_cast<std::uint64_t>(KB::in(hw[i]));
+    check(drhip_split_exact(static_cast<int>(P), n.data(), static_cast<int>(nb), g.data(), lo.data(), hi.data(),
+                            win.data(), wbits.data(), split.data()),
+          "drhip_split_exact");
+  }
+  return split;
+}
 
 } // namespace detail
 
@@ -139,7 +228,6 @@ void sort(ExecutionPolicy &&, R &&r) {
     detail::sort_general<T>(segs, std::less<>{});
     return;
   } else {
-  using KB = detail::key_bits<T>;
   std::vector<device_span<T>> parts;
   for (auto &s : segs)
     if (s.size()) parts.push_back(s);
@@ -180,48 +268,9 @@ void sort(ExecutionPolicy &&, R &&r) {
     sync(parts[0].rank());
     return;
   }
-  std::size_t tot_smp = 0;
-  for (auto v : ns) tot_smp += v;
-  detail::pinned<T> hs(tot_smp);
-  for (std::size_t k = 0, off = 0; k < P; off += ns[k], k++)
-    detail::check(drhip_memcpy_d2h(static_cast<int>(parts[k].rank()), hs.data() + off, sc[k].smp, ns[k] * sizeof(T)),
-                  "sort samples d2h");
-  for (std::size_t k = 0; k < P; k++) sync(parts[k].rank());
-
-  // 2. exact splitting at the segment boundaries (csrc/split.hip): value
-  //    brackets from the samples, then each boundary key on the slices of
-  //    every sorted segment that hold its bracket
+  // 2. exact splitting at the segment boundaries
   const std::size_t nb = P - 1;
-  std::vector<std::uint64_t> g(nb), lo(nb), hi(nb), win(2 * P * nb), split(P * (nb + 1));
-  for (std::size_t k = 0, acc = 0; k < nb; k++) g[k] = acc += n[k];
-  {
-    std::vector<std::uint64_t> bits(tot_smp);
-    for (std::size_t i = 0; i < tot_smp; i++) bits[i] = static_cast<std::uint64_t>(KB::in(hs[i]));
-    detail::check(drhip_split_windows(static_cast<int>(P), n.data(), stride.data(), ns.data(), bits.data(),
-                                      static_cast<int>(nb), g.data(), lo.data(), hi.data(), win.data()),
-                  "drhip_split_windows");
-  }
-  std::size_t tot_win = 0;
-  for (std::size_t i = 0; i < P * nb; i++) tot_win += win[2 * i + 1] - win[2 * i];
-  {
-    detail::pinned<T> hw(tot_win);
-    std::size_t off = 0;
-    for (std::size_t s = 0; s < P; s++)
-      for (std::size_t k = 0; k < nb; k++) {
-        const std::size_t a = win[2 * (s * nb + k)], b = win[2 * (s * nb + k) + 1];
-        if (b > a)
-          detail::check(drhip_memcpy_d2h(static_cast<int>(parts[s].rank()), hw.data() + off, parts[s].data() + a,
-                                         (b - a) * sizeof(T)),
-                        "sort slices d2h");
-        off += b - a;
-      }
-    for (std::size_t s = 0; s < P; s++) sync(parts[s].rank());
-    std::vector<std::uint64_t> wbits(tot_win);
-    for (std::size_t i = 0; i < tot_win; i++) wbits[i] = static_cast<std::uint64_t>(KB::in(hw[i]));
-    detail::check(drhip_split_exact(static_cast<int>(P), n.data(), static_cast<int>(nb), g.data(), lo.data(),
-                                    hi.data(), win.data(), wbits.data(), split.data()),
-                  "drhip_split_exact");
-  }
+  const std::vector<std::uint64_t> split = detail::exact_splits<T>(parts, sc, n, stride, ns);
   auto sp = [&](std::size_t s, std::size_t k) -> std::size_t { return split[s * (nb + 1) + k]; };
 
   // 3. move pieces: source s range [split[s][k-1], split[s][k]) -> dest k
@@ -475,6 +524,137 @@ void sort(ExecutionPolicy &&policy, Iter first, Iter last) {
 template <typename ExecutionPolicy, lib::distributed_iterator Iter, typename Compare>
 void sort(ExecutionPolicy &&policy, Iter first, Iter last, Compare comp) {
   shp::sort(std::forward<ExecutionPolicy>(policy), std::ranges::subrange(first, last), comp);
+}
+
+// sort_by_key(keys, values[, comp]): std::stable_sort of the (key, value)
+// pairs by key over the whole range -- equal keys keep segment order, then
+// index order within a segment.  Keys are any of the six ABI key types,
+// values any trivially copyable type of 4 or 8 bytes (moved as bits), comp
+// std::less or std::greater (any spelling).  Both ranges keep their
+// segmentation, which must agree segment by segment.  The steps are
+// shp::sort's with the values carried along:
+//   1. every segment: drhip_sort_pairs (stable LSD radix) + key samples;
+//   2. exact splitting on the keys alone (detail::exact_splits; ties go out
+//      in segment order);
+//   3. every (source, destination) piece: two device-to-device copies, keys
+//      and values, by the same split indices;
+//   4. every destination: drhip_merge_pairs_runs_to (the earlier run first
+//      on ties) straight into the key segment and the value segment.
+// std::greater sorts flipped keys ascending and flips them back
+// (detail::flip_order reverses the order and keeps equality, so the stable
+// ascending sort of the flipped keys IS the stable descending sort).
+template <typename ExecutionPolicy, typename KR, typename VR, typename Compare = std::ranges::less>
+  requires lib::distributed_contiguous_range<KR> && lib::distributed_contiguous_range<VR>
+void sort_by_key(ExecutionPolicy &&policy, KR &&keys, VR &&values, Compare comp = {}) {
+  using C = std::remove_cvref_t<Compare>;
+  using T = std::remove_cv_t<std::ranges::range_value_t<KR>>;
+  using V = std::remove_cv_t<std::ranges::range_value_t<VR>>;
+  static_assert(detail::abi_type<T>,
+                "shp::sort_by_key: keys must be int32/uint32/int64/uint64/float/double; for other records use "
+                "shp::sort on a struct with a comparator");
+  static_assert(std::is_trivially_copyable_v<V> && (sizeof(V) == 4 || sizeof(V) == 8),
+                "shp::sort_by_key: values must be trivially copyable and 4 or 8 bytes (sort an index and gather "
+                "for anything else)");
+  static_assert(detail::is_less_v<C, T> || detail::is_greater_v<C, T>,
+                "shp::sort_by_key: the comparator must be std::less or std::greater; for any other order pack key "
+                "and value into a struct and call shp::sort(range, comp)");
+  if constexpr (detail::is_greater_v<C, T>) {
+    shp::for_each(policy, keys, detail::flip_order<T>{});
+    shp::sort_by_key(policy, keys, values);
+    shp::for_each(policy, keys, detail::flip_order<T>{});
+    return;
+  } else {
+  constexpr std::size_t vb = sizeof(V);
+  if (static_cast<std::size_t>(std::ranges::size(keys)) != static_cast<std::size_t>(std::ranges::size(values)))
+    throw std::invalid_argument("shp::sort_by_key: keys and values differ in size");
+  std::vector<device_span<T>> parts;
+  std::vector<device_span<V>> vparts;
+  for (auto &&s : lib::ranges::segments(keys))
+    if (s.size()) parts.push_back(s);
+  for (auto &&s : lib::ranges::segments(values))
+    if (s.size()) vparts.push_back(s);
+  const std::size_t P = parts.size();
+  if (vparts.size() != P) throw std::invalid_argument("shp::sort_by_key: keys and values are segmented differently");
+  for (std::size_t k = 0; k < P; k++)
+    if (parts[k].size() != vparts[k].size() || parts[k].rank() != vparts[k].rank())
+      throw std::invalid_argument("shp::sort_by_key: keys and values are segmented differently");
+  if (P == 0) return;
+  std::vector<std::uint64_t> n(P), stride(P), ns(P);
+  for (std::size_t k = 0; k < P; k++) {
+    n[k] = parts[k].size();
+    stride[k] = std::max<std::uint64_t>(1, (n[k] + detail::kSortSamples - 1) / detail::kSortSamples);
+    ns[k] = (n[k] + stride[k] - 1) / stride[k];
+  }
+  std::vector<detail::sort_scratch> sc(P);
+  {
+    std::map<std::size_t, std::size_t> rank_bytes; // one scratch block per rank, carved per segment
+    for (std::size_t k = 0; k < P; k++) {
+      sc[k] = detail::size_pairs_scratch<T>(parts[k].rank(), n[k], P, ns[k], vb);
+      rank_bytes[parts[k].rank()] += sc[k].bytes;
+    }
+    std::map<std::size_t, char *> rank_next;
+    for (auto &[rk, b] : rank_bytes) rank_next[rk] = static_cast<char *>(detail::device_scratch().get(rk, b));
+    for (std::size_t k = 0; k < P; k++) {
+      char *&next = rank_next[parts[k].rank()];
+      detail::carve_pairs_scratch<T>(sc[k], next, n[k], P, vb);
+      next += sc[k].bytes;
+    }
+  }
+  // 1. local stable sorts of the pairs, then the regular key samples
+  for (std::size_t k = 0; k < P; k++) {
+    const int rk = static_cast<int>(parts[k].rank());
+    if (n[k] > 1)
+      detail::check(drhip_sort_pairs(rk, detail::dtype_code<T>(), parts[k].data(), vparts[k].data(), vb, n[k], sc[k].ws,
+                                     sc[k].wsb),
+                    "drhip_sort_pairs");
+    if (P > 1)
+      detail::check(drhip_sort_sample(rk, detail::dtype_code<T>(), parts[k].data(), n[k], stride[k], sc[k].smp),
+                    "drhip_sort_sample");
+  }
+  if (P == 1) {
+    sync(parts[0].rank());
+    return;
+  }
+  // 2. exact splitting on the keys alone
+  const std::size_t nb = P - 1;
+  const std::vector<std::uint64_t> split = detail::exact_splits<T>(parts, sc, n, stride, ns);
+  auto sp = [&](std::size_t s, std::size_t k) -> std::size_t { return split[s * (nb + 1) + k]; };
+  // 3. pieces, keys and values by the same indices, in source order
+  for (std::size_t k = 0; k < P; k++) {
+    std::size_t off = 0;
+    const int rk = static_cast<int>(parts[k].rank());
+    for (std::size_t s = 0; s < P; s++) {
+      const std::size_t a = k == 0 ? 0 : sp(s, k - 1), b = sp(s, k);
+      if (b > a) {
+        detail::check(drhip_memcpy_d2d(rk, static_cast<T *>(sc[k].buf) + off, parts[s].data() + a, (b - a) * sizeof(T)),
+                      "sort_by_key key piece copy");
+        detail::check(drhip_memcpy_d2d(rk, static_cast<V *>(sc[k].vbuf) + off, vparts[s].data() + a, (b - a) * vb),
+                      "sort_by_key value piece copy");
+      }
+      off += b - a;
+    }
+    if (off != n[k]) throw std::runtime_error("shp::sort_by_key: splitting did not balance");
+  }
+  sync_all();
+  // 4. stable merge of the P runs straight into the key and value segments
+  for (std::size_t k = 0; k < P; k++) {
+    const int rk = static_cast<int>(parts[k].rank());
+    std::vector<std::size_t> offs(P + 1, 0);
+    for (std::size_t s = 0; s < P; s++) offs[s + 1] = offs[s] + (sp(s, k) - (k == 0 ? 0 : sp(s, k - 1)));
+    detail::check(drhip_merge_pairs_runs_to(rk, detail::dtype_code<T>(), vb, sc[k].buf, sc[k].vbuf, parts[k].data(),
+                                            vparts[k].data(), n[k], offs.data(), static_cast<int>(P), sc[k].mws,
+                                            sc[k].mwsb),
+                  "drhip_merge_pairs_runs_to");
+  }
+  sync_all();
+  }
+}
+
+template <typename ExecutionPolicy, lib::distributed_iterator KIter, lib::distributed_iterator VIter,
+          typename Compare = std::ranges::less>
+void sort_by_key(ExecutionPolicy &&policy, KIter keys_first, KIter keys_last, VIter values_first, Compare comp = {}) {
+  shp::sort_by_key(std::forward<ExecutionPolicy>(policy), std::ranges::subrange(keys_first, keys_last),
+                   std::ranges::subrange(values_first, values_first + (keys_last - keys_first)), comp);
 }
 
 } // namespace shp

@@ -311,6 +311,38 @@ int drhip_merge_runs(int seg, int dtype, void *keys, size_t n, const size_t *run
  * drhip_merge_runs. */
 int drhip_merge_runs_to(int seg, int dtype, const void *src, void *dst, size_t n, const size_t *run_offsets,
                         int nruns, void *tmp, size_t tmp_bytes);
+/* Sort by key (shp::sort_by_key): keys[0, n) of kdtype (the six key types of
+ * drhip_sort) ascending, vals[i] carried with keys[i].  STABLE: pairs with
+ * equal keys keep their input order (std::stable_sort of the pairs by key).
+ * Key order as drhip_sort: std::less on the key values, -0.0 before +0.0,
+ * NaN keys not supported.  Values are val_bytes = 4 or 8 bytes each and move
+ * as bits (anything else: DRHIP_ERR_BAD_ARG).  The classic three-kernel pass
+ * per 8-bit digit at every n (the persistent passes of drhip_sort carry no
+ * payload), so DRHIP_SORT_ALGO has no effect and sorts from separate
+ * processes may share a device.  Asynchronous on the segment's stream;
+ * n < 2^32; keys key-aligned, vals aligned to val_bytes, tmp 256-byte
+ * aligned with at least drhip_sort_pairs_workspace bytes (less:
+ * DRHIP_ERR_BAD_ARG); n <= 1 returns DRHIP_OK and touches no memory.  The
+ * workspace query needs no initialised device and is never below
+ * drhip_sort_workspace(n) + n * val_bytes. */
+int drhip_sort_pairs_workspace(int seg, int kdtype, size_t val_bytes, size_t n, size_t *bytes);
+int drhip_sort_pairs(int seg, int kdtype, void *keys, void *vals, size_t val_bytes, size_t n, void *tmp,
+                     size_t tmp_bytes);
+/* drhip_merge_runs_to with a payload: src_keys[0, n) holds nruns sorted runs
+ * [run_offsets[r], run_offsets[r+1]) and src_vals the value of every key;
+ * dst_keys / dst_vals receive the merged pairs.  STABLE: on equal keys the
+ * earlier run goes first and a run keeps its own order, so runs that are
+ * stably sorted pieces in source order merge to the stable sort of the whole.
+ * Rounds alternate between tmp and dst so that the last one writes dst; a
+ * single run, or a run left unpaired in a round, is copied, keys and values
+ * alike.  src and dst key- / value-aligned and not overlapping, src
+ * unchanged; nruns <= 128; val_bytes 4 or 8; tmp 256-byte aligned with
+ * drhip_merge_pairs_workspace bytes (no initialised device needed for the
+ * query). */
+int drhip_merge_pairs_workspace(int seg, int kdtype, size_t val_bytes, size_t n, int nruns, size_t *bytes);
+int drhip_merge_pairs_runs_to(int seg, int kdtype, size_t val_bytes, const void *src_keys, const void *src_vals,
+                              void *dst_keys, void *dst_vals, size_t n, const size_t *run_offsets, int nruns,
+                              void *tmp, size_t tmp_bytes);
 
 /* ---------------------------------------------------------- stencil ----
  * mhp::transform of a radius-r 1-D stencil over a halo'd segment
