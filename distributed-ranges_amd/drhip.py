@@ -29,6 +29,9 @@ LIB_PATH = os.environ.get("DRHIP_LIB") or os.path.join(HERE, "libdrhip.so")
 
 I32, U32, I64, U64, F32, F64 = 0, 1, 2, 3, 4, 5
 PLUS, MUL, MIN, MAX = 0, 1, 2, 3
+LT, LE, GT, GE, EQ, NE = 0, 1, 2, 3, 4, 5
+CMPS = {"lt": LT, "le": LE, "gt": GT, "ge": GE, "eq": EQ, "ne": NE,
+        "<": LT, "<=": LE, ">": GT, ">=": GE, "==": EQ, "!=": NE}
 OPS = {"plus": PLUS, "mul": MUL, "min": MIN, "max": MAX}
 DTYPES = {
     np.dtype(np.int32): I32, np.dtype(np.uint32): U32, np.dtype(np.int64): I64,
@@ -54,6 +57,7 @@ EXPORTS = [
     "drhip_stencil1d", "drhip_stencil2d", "drhip_merge_workspace", "drhip_merge_runs",
     "drhip_merge_runs_to",
     "drhip_sort_pairs_workspace", "drhip_sort_pairs", "drhip_merge_pairs_workspace", "drhip_merge_pairs_runs_to",
+    "drhip_count_if", "drhip_copy_if", "drhip_copy_flagged",
     "drhip_comm_unique_id", "drhip_comm_init_rank", "drhip_comm_init_all", "drhip_comm_destroy",
     "drhip_comm_rank", "drhip_comm_group_start", "drhip_comm_group_end", "drhip_allreduce",
     "drhip_allgather", "drhip_gather", "drhip_alltoallv", "drhip_halo_exchange",
@@ -115,6 +119,8 @@ def load():
         "drhip_sort_pairs_workspace": [i, i, sz, sz, vp], "drhip_sort_pairs": [i, i, vp, vp, sz, sz, vp, sz],
         "drhip_merge_pairs_workspace": [i, i, sz, sz, i, vp],
         "drhip_merge_pairs_runs_to": [i, i, sz, vp, vp, vp, vp, sz, vp, i, vp, sz],
+        "drhip_count_if": [i, i, i, vp, sz, vp, vp], "drhip_copy_if": [i, i, i, vp, vp, sz, vp, vp],
+        "drhip_copy_flagged": [i, sz, vp, vp, vp, sz, vp],
         "drhip_comm_unique_id": [vp], "drhip_comm_init_rank": [i, i, i, vp], "drhip_comm_init_all": [],
         "drhip_comm_destroy": [i], "drhip_comm_rank": [i, vp, vp], "drhip_comm_group_start": [],
         "drhip_comm_group_end": [], "drhip_allreduce": [i, i, i, vp, vp, sz], "drhip_allgather": [i, vp, vp, sz],
@@ -430,6 +436,27 @@ def merge_pairs_runs_to(seg, kdtype, val_bytes, src_keys, src_vals, dst_keys, ds
                                            dst_vals, n, offs, len(run_offsets) - 1, tmp, tmp_bytes))
 
 
+def _cmp(cmp):
+    return CMPS[cmp] if isinstance(cmp, str) else int(cmp)
+
+
+def count_if_async(seg, dtype, cmp, x, n, scalar, count_dev):
+    """drhip_count_if: *count_dev (uint64, device-visible) = the number of x[i] cmp scalar, i < n."""
+    v = _scalar(scalar, dtype)
+    check(load().drhip_count_if(seg, DTYPES[np.dtype(dtype)], _cmp(cmp), x, n, _hp(v), count_dev))
+
+
+def copy_if_async(seg, dtype, cmp, src, dst, n, scalar, count_dev):
+    """drhip_copy_if: dst[0, *count_dev) = the src[i] with src[i] cmp scalar, in input order."""
+    v = _scalar(scalar, dtype)
+    check(load().drhip_copy_if(seg, DTYPES[np.dtype(dtype)], _cmp(cmp), src, dst, n, _hp(v), count_dev))
+
+
+def copy_flagged_async(seg, elem_bytes, src, flags, dst, n, count_dev):
+    """drhip_copy_flagged: dst[0, *count_dev) = the src[i] (elem_bytes = 4 or 8 each) with flags[i] != 0."""
+    check(load().drhip_copy_flagged(seg, elem_bytes, src, flags, dst, n, count_dev))
+
+
 def sort_sample(seg, dtype, sorted_ptr, n, stride, samples):
     """samples[j] = sorted[j * stride], j < ceil(n / stride)."""
     check(load().drhip_sort_sample(seg, DTYPES[np.dtype(dtype)], sorted_ptr, n, stride, samples))
@@ -562,3 +589,27 @@ def reduce(seg, x_ptr, n, dtype, op="plus"):
     r = out.numpy()[0]
     out.free()
     return r
+
+
+def _with_count(seg, call):
+    out = DeviceArray(seg, 1, np.uint64)
+    try:
+        call(out.ptr)
+        return int(out.numpy()[0])
+    finally:
+        out.free()
+
+
+def count_if(seg, x_ptr, n, dtype, cmp, scalar):
+    """The number of the n elements at device address x_ptr with x[i] cmp scalar (blocking)."""
+    return _with_count(seg, lambda c: count_if_async(seg, dtype, cmp, x_ptr, n, scalar, c))
+
+
+def copy_if(seg, src_ptr, dst_ptr, n, dtype, cmp, scalar):
+    """Copies the src[i] with src[i] cmp scalar to dst in input order (blocking); returns their number."""
+    return _with_count(seg, lambda c: copy_if_async(seg, dtype, cmp, src_ptr, dst_ptr, n, scalar, c))
+
+
+def copy_flagged(seg, src_ptr, flags_ptr, dst_ptr, n, elem_bytes):
+    """Copies the src[i] with flags[i] != 0 to dst in input order (blocking); returns their number."""
+    return _with_count(seg, lambda c: copy_flagged_async(seg, elem_bytes, src_ptr, flags_ptr, dst_ptr, n, c))

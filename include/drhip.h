@@ -344,6 +344,45 @@ int drhip_merge_pairs_runs_to(int seg, int kdtype, size_t val_bytes, const void 
                               void *dst_keys, void *dst_vals, size_t n, const size_t *run_offsets, int nruns,
                               void *tmp, size_t tmp_bytes);
 
+/* ----------------------------------------------------------- select ----
+ * copy_if / count_if are absent from the reference (its shp algorithms stop
+ * at for_each / reduce / inclusive_scan / gemv); defined with the semantics
+ * of std::count_if / std::copy_if: the elements that satisfy the predicate,
+ * in input order (stable).  What they replace is a copy of the segment to
+ * the host and a host loop.  One single-pass kernel per call (tile ranks by
+ * ballots, the tiles' offsets by a decoupled look-back over one 8-byte
+ * {status, count} word per tile; include/dr/details/select_kernel.hpp): the
+ * input is read once and only the survivors are written.
+ * The predicate is `x[i] cmp *scalar_host` with the C++ operator of the
+ * element type (the six dtypes), so IEEE rules hold for floats: a NaN passes
+ * only DRHIP_NE, and -0.0 == +0.0.  scalar_host (element type) is read
+ * during the call.
+ * Asynchronous on the segment's stream.  *count (uint64, device-visible:
+ * device or pinned host memory, not null) is written by the kernel; with
+ * n == 0 it still receives 0 in stream order and nothing else is touched.
+ * `out` needs room for the number selected -- a caller who does not know it
+ * passes room for n -- and elements of out at or past *count are never
+ * written.  out must not overlap in (or flags): DRHIP_ERR_BAD_ARG.  An
+ * unknown dtype or cmp, elem_bytes outside {4, 8}, a null pointer with n > 0,
+ * a null count and n >= 2^32 (counts are 32-bit inside the kernel) are
+ * DRHIP_ERR_BAD_ARG too; the arguments are checked before the segment, so a
+ * refusal leaves *count untouched.  The status words live in the segment's
+ * workspace, which grows on demand -- not while a graph of the segment is
+ * alive or being captured (DRHIP_ERR_UNSUPPORTED, see drhip_graph_begin:
+ * warm up with one eager call at the largest n); they are re-zeroed by a
+ * memset node before every launch, so a graph replay recomputes everything. */
+typedef enum { DRHIP_LT = 0, DRHIP_LE = 1, DRHIP_GT = 2, DRHIP_GE = 3, DRHIP_EQ = 4, DRHIP_NE = 5 } drhip_cmp;
+/* *count = |{ i < n : x[i] cmp *scalar_host }| (4 B/elem read, nothing written but *count) */
+int drhip_count_if(int seg, int dtype, int cmp, const void *x, size_t n, const void *scalar_host, uint64_t *count);
+/* out[0..*count) = the elements of in[0..n) with in[i] cmp *scalar_host, in input order */
+int drhip_copy_if(int seg, int dtype, int cmp, const void *in, void *out, size_t n, const void *scalar_host,
+                  uint64_t *count);
+/* The same with flags[i] != 0 as the predicate (one byte per element, e.g.
+ * the mask another kernel left); elements move as bits, elem_bytes = 4 or 8,
+ * in and out aligned to elem_bytes. */
+int drhip_copy_flagged(int seg, size_t elem_bytes, const void *in, const uint8_t *flags, void *out, size_t n,
+                       uint64_t *count);
+
 /* ---------------------------------------------------------- stencil ----
  * mhp::transform of a radius-r 1-D stencil over a halo'd segment
  * (mhp/algorithms/cpu_algorithms.hpp:147-161 with the ops of
