@@ -58,6 +58,7 @@ EXPORTS = [
     "drhip_merge_runs_to",
     "drhip_sort_pairs_workspace", "drhip_sort_pairs", "drhip_merge_pairs_workspace", "drhip_merge_pairs_runs_to",
     "drhip_count_if", "drhip_copy_if", "drhip_copy_flagged",
+    "drhip_reduce_by_key", "drhip_run_length_encode", "drhip_unique_copy",
     "drhip_comm_unique_id", "drhip_comm_init_rank", "drhip_comm_init_all", "drhip_comm_destroy",
     "drhip_comm_rank", "drhip_comm_group_start", "drhip_comm_group_end", "drhip_allreduce",
     "drhip_allgather", "drhip_gather", "drhip_alltoallv", "drhip_halo_exchange",
@@ -121,6 +122,8 @@ def load():
         "drhip_merge_pairs_runs_to": [i, i, sz, vp, vp, vp, vp, sz, vp, i, vp, sz],
         "drhip_count_if": [i, i, i, vp, sz, vp, vp], "drhip_copy_if": [i, i, i, vp, vp, sz, vp, vp],
         "drhip_copy_flagged": [i, sz, vp, vp, vp, sz, vp],
+        "drhip_reduce_by_key": [i, i, i, i, vp, vp, sz, vp, vp, vp],
+        "drhip_run_length_encode": [i, i, vp, sz, vp, vp, vp], "drhip_unique_copy": [i, i, vp, sz, vp, vp],
         "drhip_comm_unique_id": [vp], "drhip_comm_init_rank": [i, i, i, vp], "drhip_comm_init_all": [],
         "drhip_comm_destroy": [i], "drhip_comm_rank": [i, vp, vp], "drhip_comm_group_start": [],
         "drhip_comm_group_end": [], "drhip_allreduce": [i, i, i, vp, vp, sz], "drhip_allgather": [i, vp, vp, sz],
@@ -457,6 +460,27 @@ def copy_flagged_async(seg, elem_bytes, src, flags, dst, n, count_dev):
     check(load().drhip_copy_flagged(seg, elem_bytes, src, flags, dst, n, count_dev))
 
 
+def _op(op):
+    return OPS[op] if isinstance(op, str) else int(op)
+
+
+def reduce_by_key_async(seg, kdtype, vdtype, op, keys, vals, n, keys_out, vals_out, runs_dev):
+    """drhip_reduce_by_key: per run of equal consecutive keys, its first key and the fold of its values;
+    *runs_dev (uint64, device-visible) = the number of runs."""
+    check(load().drhip_reduce_by_key(seg, DTYPES[np.dtype(kdtype)], DTYPES[np.dtype(vdtype)], _op(op), keys, vals, n,
+                                     keys_out, vals_out, runs_dev))
+
+
+def run_length_encode_async(seg, kdtype, keys, n, keys_out, counts_out, runs_dev):
+    """drhip_run_length_encode: per run its first key and its length (uint64)."""
+    check(load().drhip_run_length_encode(seg, DTYPES[np.dtype(kdtype)], keys, n, keys_out, counts_out, runs_dev))
+
+
+def unique_copy_async(seg, kdtype, keys, n, keys_out, runs_dev):
+    """drhip_unique_copy: the first key of every run of equal consecutive keys."""
+    check(load().drhip_unique_copy(seg, DTYPES[np.dtype(kdtype)], keys, n, keys_out, runs_dev))
+
+
 def sort_sample(seg, dtype, sorted_ptr, n, stride, samples):
     """samples[j] = sorted[j * stride], j < ceil(n / stride)."""
     check(load().drhip_sort_sample(seg, DTYPES[np.dtype(dtype)], sorted_ptr, n, stride, samples))
@@ -613,3 +637,19 @@ def copy_if(seg, src_ptr, dst_ptr, n, dtype, cmp, scalar):
 def copy_flagged(seg, src_ptr, flags_ptr, dst_ptr, n, elem_bytes):
     """Copies the src[i] with flags[i] != 0 to dst in input order (blocking); returns their number."""
     return _with_count(seg, lambda c: copy_flagged_async(seg, elem_bytes, src_ptr, flags_ptr, dst_ptr, n, c))
+
+
+def reduce_by_key(seg, keys_ptr, vals_ptr, n, kdtype, vdtype, keys_out_ptr, vals_out_ptr, op="plus"):
+    """Folds every run of equal consecutive keys (blocking); returns the number of runs."""
+    return _with_count(seg, lambda c: reduce_by_key_async(seg, kdtype, vdtype, op, keys_ptr, vals_ptr, n, keys_out_ptr,
+                                                          vals_out_ptr, c))
+
+
+def run_length_encode(seg, keys_ptr, n, kdtype, keys_out_ptr, counts_out_ptr):
+    """Every run's first key and length (uint64) (blocking); returns the number of runs."""
+    return _with_count(seg, lambda c: run_length_encode_async(seg, kdtype, keys_ptr, n, keys_out_ptr, counts_out_ptr, c))
+
+
+def unique_copy(seg, keys_ptr, n, kdtype, keys_out_ptr):
+    """Every run's first key (blocking); returns the number of runs."""
+    return _with_count(seg, lambda c: unique_copy_async(seg, kdtype, keys_ptr, n, keys_out_ptr, c))

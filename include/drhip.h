@@ -383,6 +383,51 @@ int drhip_copy_if(int seg, int dtype, int cmp, const void *in, void *out, size_t
 int drhip_copy_flagged(int seg, size_t elem_bytes, const void *in, const uint8_t *flags, void *out, size_t n,
                        uint64_t *count);
 
+/* ---------------------------------------------------- reduce by key ----
+ * The second half of a sort_by_key pipeline (group-by, combining duplicate
+ * COO entries, row counts for a CSR rowptr); absent from the reference,
+ * defined with the semantics of thrust::reduce_by_key / std::unique_copy.
+ * A run is a maximal stretch of consecutive elements whose neighbouring keys
+ * compare equal; element 0 starts a run.  Run r gives keys_out[r] = the bits
+ * of the run's FIRST key and vals_out[r] = the fold of the run's values in
+ * input order; the outputs are contiguous from the start and nothing at or
+ * past index *num_runs is written.  Keys compare with the C++ == of the key
+ * type (the six dtypes; IEEE for floats: -0.0 and +0.0 share a run, whose
+ * key is the first one's bits, and every NaN key is a run of its own).
+ * Values (the six dtypes) fold under DRHIP_PLUS / MUL / MIN / MAX as in
+ * drhip_reduce: integers wrap; floats are folded in double, in the tile and
+ * between tiles, and the output element is the value dtype, rounded once.
+ * The fold may associate differently from a sequential loop but never
+ * reorders: it is bit-exact whenever every partial result is representable.
+ * One single-pass kernel (include/dr/details/segreduce_kernel.hpp: heads
+ * ranked by ballots, only the 32-bit head count crosses workgroups through
+ * select's look-back word, a segmented fold inside the tile) and one small
+ * fix-up kernel that folds the runs left open at tile boundaries.
+ * drhip_run_length_encode is the same kernel with a constant value 1 under
+ * PLUS (no value stream is read; n < 2^32, so the counts are 4 bytes inside
+ * the kernel and widened at the stores; counts_out is uint64, so a run of
+ * any length fits once calls are joined); drhip_unique_copy writes the keys only.
+ * Asynchronous on the segment's stream.  *num_runs (uint64, device-visible,
+ * not null) is written by the kernel; with n == 0 it still receives 0 in
+ * stream order and nothing else is touched.  The outputs need room for the
+ * number of runs -- a caller who does not know it passes room for n.
+ * DRHIP_ERR_BAD_ARG: an unknown dtype or op, a null pointer with n > 0, a
+ * null num_runs, n >= 2^32 (counts are 32-bit inside the kernel), any output
+ * overlapping any input (taken over n elements).  The arguments are checked
+ * before the segment, so a refusal leaves *num_runs untouched.  The state
+ * (tile counter, status words, tile records) lives in the segment's
+ * workspace, which grows on demand -- not while a graph of the segment is
+ * alive or being captured (DRHIP_ERR_UNSUPPORTED: warm up with one eager call
+ * at the largest n, as for drhip_copy_if); it is re-zeroed by a memset node
+ * before every launch, so a graph replay recomputes everything. */
+int drhip_reduce_by_key(int seg, int kdtype, int vdtype, int op, const void *keys_in, const void *vals_in, size_t n,
+                        void *keys_out, void *vals_out, uint64_t *num_runs);
+/* keys_out[r], counts_out[r] = the first key and the length of run r */
+int drhip_run_length_encode(int seg, int kdtype, const void *keys_in, size_t n, void *keys_out, uint64_t *counts_out,
+                            uint64_t *num_runs);
+/* keys_out[r] = the first key of run r */
+int drhip_unique_copy(int seg, int kdtype, const void *keys_in, size_t n, void *keys_out, uint64_t *num_runs);
+
 /* ---------------------------------------------------------- stencil ----
  * mhp::transform of a radius-r 1-D stencil over a halo'd segment
  * (mhp/algorithms/cpu_algorithms.hpp:147-161 with the ops of
