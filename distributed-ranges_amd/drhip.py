@@ -59,6 +59,7 @@ EXPORTS = [
     "drhip_sort_pairs_workspace", "drhip_sort_pairs", "drhip_merge_pairs_workspace", "drhip_merge_pairs_runs_to",
     "drhip_count_if", "drhip_copy_if", "drhip_copy_flagged",
     "drhip_reduce_by_key", "drhip_run_length_encode", "drhip_unique_copy",
+    "drhip_inclusive_scan_by_key", "drhip_exclusive_scan_by_key",
     "drhip_comm_unique_id", "drhip_comm_init_rank", "drhip_comm_init_all", "drhip_comm_destroy",
     "drhip_comm_rank", "drhip_comm_group_start", "drhip_comm_group_end", "drhip_allreduce",
     "drhip_allgather", "drhip_gather", "drhip_alltoallv", "drhip_halo_exchange",
@@ -124,6 +125,8 @@ def load():
         "drhip_copy_flagged": [i, sz, vp, vp, vp, sz, vp],
         "drhip_reduce_by_key": [i, i, i, i, vp, vp, sz, vp, vp, vp],
         "drhip_run_length_encode": [i, i, vp, sz, vp, vp, vp], "drhip_unique_copy": [i, i, vp, sz, vp, vp],
+        "drhip_inclusive_scan_by_key": [i, i, i, i, vp, vp, sz, vp],
+        "drhip_exclusive_scan_by_key": [i, i, i, i, vp, vp, sz, vp, vp],
         "drhip_comm_unique_id": [vp], "drhip_comm_init_rank": [i, i, i, vp], "drhip_comm_init_all": [],
         "drhip_comm_destroy": [i], "drhip_comm_rank": [i, vp, vp], "drhip_comm_group_start": [],
         "drhip_comm_group_end": [], "drhip_allreduce": [i, i, i, vp, vp, sz], "drhip_allgather": [i, vp, vp, sz],
@@ -481,6 +484,21 @@ def unique_copy_async(seg, kdtype, keys, n, keys_out, runs_dev):
     check(load().drhip_unique_copy(seg, DTYPES[np.dtype(kdtype)], keys, n, keys_out, runs_dev))
 
 
+def inclusive_scan_by_key_async(seg, kdtype, vdtype, op, keys, vals, n, vals_out):
+    """drhip_inclusive_scan_by_key: vals_out[i] = the fold of the values of i's run of equal consecutive keys up to
+    and including i (vals_out may be vals)."""
+    check(load().drhip_inclusive_scan_by_key(seg, DTYPES[np.dtype(kdtype)], DTYPES[np.dtype(vdtype)], _op(op), keys, vals,
+                                             n, vals_out))
+
+
+def exclusive_scan_by_key_async(seg, kdtype, vdtype, op, keys, vals, n, vals_out, init=None):
+    """drhip_exclusive_scan_by_key: vals_out[i] = init op the values of i's run before i; a run's first element
+    gets init (None: the identity of op)."""
+    v = None if init is None else _scalar(init, vdtype)
+    check(load().drhip_exclusive_scan_by_key(seg, DTYPES[np.dtype(kdtype)], DTYPES[np.dtype(vdtype)], _op(op), keys, vals,
+                                             n, _hp(v), vals_out))
+
+
 def sort_sample(seg, dtype, sorted_ptr, n, stride, samples):
     """samples[j] = sorted[j * stride], j < ceil(n / stride)."""
     check(load().drhip_sort_sample(seg, DTYPES[np.dtype(dtype)], sorted_ptr, n, stride, samples))
@@ -653,3 +671,15 @@ def run_length_encode(seg, keys_ptr, n, kdtype, keys_out_ptr, counts_out_ptr):
 def unique_copy(seg, keys_ptr, n, kdtype, keys_out_ptr):
     """Every run's first key (blocking); returns the number of runs."""
     return _with_count(seg, lambda c: unique_copy_async(seg, kdtype, keys_ptr, n, keys_out_ptr, c))
+
+
+def inclusive_scan_by_key(seg, keys_ptr, vals_ptr, n, kdtype, vdtype, vals_out_ptr, op="plus"):
+    """The running fold of every run of equal consecutive keys (blocking)."""
+    inclusive_scan_by_key_async(seg, kdtype, vdtype, op, keys_ptr, vals_ptr, n, vals_out_ptr)
+    sync(seg)
+
+
+def exclusive_scan_by_key(seg, keys_ptr, vals_ptr, n, kdtype, vdtype, vals_out_ptr, op="plus", init=None):
+    """The running fold of every run before each element, seeded with init (blocking)."""
+    exclusive_scan_by_key_async(seg, kdtype, vdtype, op, keys_ptr, vals_ptr, n, vals_out_ptr, init)
+    sync(seg)

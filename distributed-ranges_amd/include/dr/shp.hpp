@@ -10,6 +10,7 @@
 #include "shp/sort.hpp"
 #include "shp/select.hpp"
 #include "shp/reduce_by_key.hpp"
+#include "shp/scan_by_key.hpp"
 #include "shp/vector.hpp"
 #include "shp/sparse.hpp"
 #include "shp/dense.hpp"

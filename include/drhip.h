@@ -428,6 +428,52 @@ int drhip_run_length_encode(int seg, int kdtype, const void *keys_in, size_t n, 
 /* keys_out[r] = the first key of run r */
 int drhip_unique_copy(int seg, int kdtype, const void *keys_in, size_t n, void *keys_out, uint64_t *num_runs);
 
+/* ------------------------------------------------------ scan by key -----
+ * Absent from the reference; defined as thrust::inclusive_scan_by_key /
+ * thrust::exclusive_scan_by_key: every element is kept and receives the
+ * running fold of its own run.  A run is what drhip_reduce_by_key calls a
+ * run: a maximal stretch of consecutive elements whose neighbouring keys
+ * compare equal; element 0 starts one.  For element i of a run starting at s
+ *   inclusive: vals_out[i] = v[s] op v[s+1] op ... op v[i]
+ *   exclusive: vals_out[i] = init op v[s] op ... op v[i-1], so the first
+ *              element of every run receives init.
+ * Per-group running totals and running min / max, the rank of an element
+ * inside its group (exclusive, PLUS, values all 1), the offset of a COO entry
+ * inside its row.  Keys compare with the C++ == of the key type (the six
+ * dtypes; IEEE for floats: -0.0 and +0.0 share a run, every NaN key is a run
+ * of its own).  Values (the six dtypes) fold under DRHIP_PLUS / MUL / MIN /
+ * MAX as in drhip_reduce_by_key: integers wrap; floats are folded in double,
+ * in the tile and between tiles, and every output element is the value
+ * dtype, rounded once.  The folds run in input order: they may associate
+ * differently from a sequential loop but never reorder, and they are
+ * bit-exact whenever every partial result is representable.
+ * init_host (exclusive only; host memory, one element of the value dtype,
+ * read during the call) may be null: the identity of op, as drhip_reduce
+ * defines it (0, 1, +inf / the type's maximum, -inf / the type's lowest).
+ * One single-pass kernel (include/dr/details/segscan_kernel.hpp): the loads,
+ * head flags and in-tile segmented fold of the reduce, and a decoupled
+ * look-back over the tiles' {has_head, fold of the open run} summaries in
+ * 8-byte self-validating words.  A tile with a head publishes at once, only a
+ * tile whose first element continues a run looks back, and the look-back ends
+ * at the nearest tile with a head.  sizeof key + 2 sizeof value bytes move per
+ * element.  vals_out may be vals_in itself (in place).
+ * Asynchronous on the segment's stream.  n == 0 returns DRHIP_OK and touches
+ * nothing.  DRHIP_ERR_BAD_ARG: an unknown dtype or op, a null keys_in,
+ * vals_in or vals_out with n > 0, n >= 2^32, vals_out overlapping keys_in,
+ * vals_out overlapping vals_in in any way other than vals_out == vals_in
+ * (ranges taken over n elements).  The arguments are checked before the
+ * segment.  The state (tile counter, one status granule per tile) lives in
+ * the segment's workspace, which grows on demand -- not while a graph of the
+ * segment is alive or being captured (DRHIP_ERR_UNSUPPORTED: warm up with one
+ * eager call at the largest n, as for drhip_copy_if); it is re-zeroed by a
+ * memset node before every launch, so a graph replay recomputes everything.
+ * A look-back that waits past the spin bound sets the segment's error word
+ * (DRHIP_ERR_TIMEOUT at drhip_sync). */
+int drhip_inclusive_scan_by_key(int seg, int kdtype, int vdtype, int op, const void *keys_in, const void *vals_in, size_t n,
+                                void *vals_out);
+int drhip_exclusive_scan_by_key(int seg, int kdtype, int vdtype, int op, const void *keys_in, const void *vals_in, size_t n,
+                                const void *init_host, void *vals_out);
+
 /* ---------------------------------------------------------- stencil ----
  * mhp::transform of a radius-r 1-D stencil over a halo'd segment
  * (mhp/algorithms/cpu_algorithms.hpp:147-161 with the ops of
