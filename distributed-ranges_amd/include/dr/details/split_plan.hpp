@@ -322,4 +322,36 @@ inline const char *split_exact_cmp(int p, const u64 *n, int nb, const u64 *g, co
   return nullptr;
 }
 
+// ---- the arithmetic around the two steps that every tier of shp::sort shares
+
+// Step 1: the regular samples of a sorted run of n keys, keys[j * stride] for
+// j < ns.  A stride of ceil(n / kSortSamples) keeps every boundary's bracket
+// to a few strides of keys per run.
+constexpr u64 kSortSamples = u64(1) << 16;
+struct sample_plan {
+  u64 stride, ns;
+};
+inline sample_plan plan_samples(u64 n) {
+  const u64 stride = std::max<u64>(1, (n + kSortSamples - 1) / kSortSamples);
+  return {stride, (n + stride - 1) / stride};
+}
+
+// The data exchange that follows step 4: what destination k of a split table
+// with nd columns (split[s * nd + k], p sources) receives.  Source s sends its keys
+// [from[s], from[s] + offs[s + 1] - offs[s]), which land at offs[s] in the
+// destination's buffer -- the runs in source order, so a stable merge that
+// takes the earlier run first on ties keeps segment order.  offs[p] is the
+// destination's size.
+struct run_plan {
+  std::vector<std::size_t> from, offs;
+};
+inline run_plan plan_runs(const u64 *split, int p, int nd, int k) {
+  run_plan r{std::vector<std::size_t>(p), std::vector<std::size_t>(p + 1, 0)};
+  for (int s = 0; s < p; s++) {
+    r.from[s] = k ? split[(std::size_t)s * nd + k - 1] : 0;
+    r.offs[s + 1] = r.offs[s] + (split[(std::size_t)s * nd + k] - r.from[s]);
+  }
+  return r;
+}
+
 } // namespace dr_plan

@@ -22,7 +22,8 @@
 // values under std::plus / std::multiplies fold in double inside a piece.
 //
 //   1. every non-empty piece is reduced on its own segment stream, all pieces
-//      concurrently, into that segment's detail::device_scratch();
+//      concurrently, into its slice of that segment's device scratch
+//      (detail::carve_scratch);
 //   2. a one-thread kernel behind it leaves the piece's boundary record in
 //      pinned memory: run count, first and last key, and the folds of the first
 //      and last run in ACC (double for float values under the library's
@@ -38,7 +39,8 @@
 //      above size(keys_out) or size(values_out) throws std::out_of_range before
 //      anything is written;
 //   5. each piece's runs are copied into the outputs with drhip_memcpy_d2d,
-//      split at output segment boundaries; the first run of a joined piece is
+//      split at output segment boundaries (detail::out_cursor, select.hpp,
+//      one per output); the first run of a joined piece is
 //      skipped and the folded value replaces the previous owner's last;
 //   6. sync.
 // Everything carried between tiles and between segments is ACC and every
@@ -143,6 +145,10 @@ struct by_key_events {
     ev.push_back(e);
     hip_check(hipEventRecord(e, st), "hipEventRecord");
   }
+  // what is enqueued on st from here on runs behind everything recorded
+  void wait_on(hipStream_t st) {
+    for (auto &e : ev) hip_check(hipStreamWaitEvent(st, e, 0), "hipStreamWaitEvent");
+  }
 };
 
 template <typename V> struct by_key_const_accessor {
@@ -167,23 +173,6 @@ template <typename Eq> struct by_key_eq {
 template <typename S, typename K> constexpr bool by_key_span_of() {
   if constexpr (is_device_span<S>) return std::is_same_v<std::remove_const_t<typename S::value_type>, K>;
   else return false;
-}
-
-// `n` elements of `src` (device memory of segment rank `rk`) into osegs from position (oi, ooff) on
-template <typename T, typename OSegs>
-void by_key_emit(const OSegs &osegs, std::size_t &oi, std::size_t &ooff, std::size_t rk, const T *src, std::size_t c) {
-  while (c) {
-    if (ooff == osegs[oi].size()) {
-      oi++;
-      ooff = 0;
-      continue;
-    }
-    const std::size_t m = std::min(c, osegs[oi].size() - ooff);
-    check(drhip_memcpy_d2d(static_cast<int>(rk), osegs[oi].data() + ooff, src, m * sizeof(T)), "drhip_memcpy_d2d");
-    src += m;
-    ooff += m;
-    c -= m;
-  }
 }
 
 // reduce: keys, values -> kout, vout.  lengths: keys -> kout, vout (values
@@ -218,35 +207,20 @@ std::size_t by_key(const char *what, KR &&keys, VR &&values, KO &&kout, VO &&vou
   if constexpr (M == by_key_mode::reduce) {
     if (static_cast<std::size_t>(std::ranges::size(keys)) != static_cast<std::size_t>(std::ranges::size(values)))
       throw std::invalid_argument(std::string(what) + ": keys and values differ in size");
-    if (vsegs.size() != P) throw std::invalid_argument(std::string(what) + ": keys and values are segmented differently");
-    for (std::size_t k = 0; k < P; k++)
-      if (ksegs[k].size() != vsegs[k].size() || ksegs[k].rank() != vsegs[k].rank())
-        throw std::invalid_argument(std::string(what) + ": keys and values are segmented differently");
+    check_segmented_alike(what, ksegs, vsegs);
   }
-  for (auto &s : ksegs)
-    if (static_cast<unsigned long long>(s.size()) >= (1ull << 32))
-      throw std::length_error(std::string(what) + ": a piece of 2^32 elements or more on one segment");
+  check_piece_sizes(what, ksegs);
 
-  // per segment: [keys of the runs | values of the runs | state] for each of its pieces
-  struct piece {
-    std::size_t tk = 0, tv = 0, state = 0;
-  };
-  std::vector<piece> lay(P);
-  std::vector<std::size_t> need(nprocs(), 0);
+  // per non-empty piece: [keys of the runs | values of the runs | state]
+  enum { TK, TV, STATE };
+  std::vector<scratch_layout<3>> lay(P);
+  std::vector<std::size_t> rank(P);
   for (std::size_t k = 0; k < P; k++) {
     const std::size_t n = ksegs[k].size();
-    if (!n) continue;
-    std::size_t &b = need.at(ksegs[k].rank());
-    lay[k].tk = b;
-    b += sel_round(n * sizeof(K));
-    lay[k].tv = b;
-    if constexpr (HASV) b += sel_round(n * sizeof(V));
-    lay[k].state = b;
-    b += sel_round(sr_state_bytes_max<K, V>(n));
+    rank[k] = ksegs[k].rank();
+    if (n) lay[k] = {n * sizeof(K), HASV ? n * sizeof(V) : 0, sr_state_bytes_max<K, V>(n)};
   }
-  std::vector<char *> base(need.size(), nullptr);
-  for (std::size_t rk = 0; rk < need.size(); rk++)
-    if (need[rk]) base[rk] = static_cast<char *>(device_scratch().get(rk, need[rk]));
+  const std::vector<char *> base = carve_scratch(rank, lay);
 
   using Edge = by_key_edge<K, V, A>;
   pinned<Edge> edge(P);
@@ -260,9 +234,9 @@ std::size_t by_key(const char *what, KR &&keys, VR &&values, KO &&kout, VO &&vou
     if (!n) continue;
     const std::size_t rk = ksegs[k].rank();
     hipStream_t st = stream(rk);
-    K *tk = reinterpret_cast<K *>(base[rk] + lay[k].tk);
-    V *tv = reinterpret_cast<V *>(base[rk] + lay[k].tv);
-    const sr_args a{base[rk] + lay[k].state, &edge[k].count, err.data()};
+    K *tk = lay[k].template at<K>(base[k], TK);
+    V *tv = lay[k].template at<V>(base[k], TV);
+    const sr_args a{lay[k].at(base[k], STATE), &edge[k].count, err.data()};
     if constexpr (M == by_key_mode::unique) {
       if constexpr (by_key_span_of<KSeg, K>())
         hip_check(sr_launch_unique<K>(st, static_cast<const K *>(ksegs[k].data()), n, tk, eq, a), "unique_copy launch");
@@ -304,7 +278,7 @@ std::size_t by_key(const char *what, KR &&keys, VR &&values, KO &&kout, VO &&vou
   if (first < 0) return 0;
   {
     const std::size_t rk = ksegs[first].rank();
-    for (auto &e : events.ev) hip_check(hipStreamWaitEvent(stream(rk), e, 0), "hipStreamWaitEvent");
+    events.wait_on(stream(rk));
     hipLaunchKernelGGL((by_key_stitch_kernel<K, V, A, HASV, by_key_eq<Eq>, by_key_op<A, Op>>), dim3(1), dim3(1), 0, stream(rk),
                        edge.data(), P, eq, op);
     hip_check(hipGetLastError(), "by-key stitch launch");
@@ -320,18 +294,17 @@ std::size_t by_key(const char *what, KR &&keys, VR &&values, KO &&kout, VO &&vou
                             (HASV ? " and " + std::to_string(std::ranges::size(vout)) : std::string()));
 
   // the pieces' runs, in order, into the outputs' segments
-  std::size_t koi = 0, kooff = 0, voi = 0, vooff = 0;
+  out_cursor<decltype(kosegs)> kcur{&kosegs};
+  out_cursor<decltype(vosegs)> vcur{&vosegs};
   for (std::size_t k = 0; k < P; k++) {
     if (!edge[k].count) continue;
     const std::size_t rk = ksegs[k].rank(), j = edge[k].joined, c = static_cast<std::size_t>(edge[k].count) - j;
     if (!c) continue;
-    by_key_emit(kosegs, koi, kooff, rk, reinterpret_cast<const K *>(base[rk] + lay[k].tk) + j, c);
+    kcur.emit(rk, lay[k].template at<const K>(base[k], TK) + j, c);
     if constexpr (HASV) {
-      by_key_emit(vosegs, voi, vooff, rk, reinterpret_cast<const V *>(base[rk] + lay[k].tv) + j, c);
-      // (voi, vooff) is just past this piece's last run
-      if (edge[k].has_edge)
-        check(drhip_memcpy_h2d(static_cast<int>(rk), vosegs[voi].data() + (vooff - 1), &edge[k].edge_val, sizeof(V)),
-              "drhip_memcpy_h2d");
+      vcur.emit(rk, lay[k].template at<const V>(base[k], TV) + j, c);
+      if (edge[k].has_edge) // on this piece's last run
+        check(drhip_memcpy_h2d(static_cast<int>(rk), vcur.last(), &edge[k].edge_val, sizeof(V)), "drhip_memcpy_h2d");
     }
   }
   select_sync(ksegs);
@@ -373,15 +346,7 @@ auto unique_copy(ExecutionPolicy &&, R &&in, O &&out, KeyEqual key_equal = KeyEq
 }
 
 // iterator forms: an output starts at its iterator and has room for the runs
-// (at most last - first are written; it is taken to end with its container
-// if that comes sooner)
-namespace detail {
-template <typename OutputIter> auto by_key_out(OutputIter d_first, std::size_t n) {
-  std::size_t room = 0;
-  for (auto &s : d_first.segments()) room += s.size();
-  return std::ranges::subrange(d_first, d_first + static_cast<std::ptrdiff_t>(std::min(room, n)));
-}
-} // namespace detail
+// (at most last - first are written)
 template <typename ExecutionPolicy, lib::distributed_iterator KIter, lib::distributed_iterator VIter,
           lib::distributed_iterator KOut, lib::distributed_iterator VOut, typename KeyEqual = std::equal_to<>,
           typename Op = std::plus<>>
@@ -390,7 +355,7 @@ std::pair<KOut, VOut> reduce_by_key(ExecutionPolicy &&policy, KIter kfirst, KIte
   const std::size_t n = static_cast<std::size_t>(klast - kfirst);
   return shp::reduce_by_key(std::forward<ExecutionPolicy>(policy), std::ranges::subrange(kfirst, klast),
                             std::ranges::subrange(vfirst, vfirst + static_cast<std::ptrdiff_t>(n)),
-                            detail::by_key_out(keys_out, n), detail::by_key_out(values_out, n), key_equal, op);
+                            detail::out_from(keys_out, n), detail::out_from(values_out, n), key_equal, op);
 }
 template <typename ExecutionPolicy, lib::distributed_iterator KIter, lib::distributed_iterator KOut,
           lib::distributed_iterator COut, typename KeyEqual = std::equal_to<>>
@@ -398,13 +363,13 @@ std::pair<KOut, COut> run_length_encode(ExecutionPolicy &&policy, KIter first, K
                                         KeyEqual key_equal = KeyEqual{}) {
   const std::size_t n = static_cast<std::size_t>(last - first);
   return shp::run_length_encode(std::forward<ExecutionPolicy>(policy), std::ranges::subrange(first, last),
-                                detail::by_key_out(keys_out, n), detail::by_key_out(counts_out, n), key_equal);
+                                detail::out_from(keys_out, n), detail::out_from(counts_out, n), key_equal);
 }
 template <typename ExecutionPolicy, lib::distributed_iterator Iter, lib::distributed_iterator OutputIter,
           typename KeyEqual = std::equal_to<>>
 OutputIter unique_copy(ExecutionPolicy &&policy, Iter first, Iter last, OutputIter d_first, KeyEqual key_equal = KeyEqual{}) {
   return shp::unique_copy(std::forward<ExecutionPolicy>(policy), std::ranges::subrange(first, last),
-                          detail::by_key_out(d_first, static_cast<std::size_t>(last - first)), key_equal);
+                          detail::out_from(d_first, static_cast<std::size_t>(last - first)), key_equal);
 }
 
 } // namespace shp

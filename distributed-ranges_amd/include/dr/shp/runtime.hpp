@@ -16,6 +16,7 @@
 
 #include <algorithm>
 #include <cstddef>
+#include <initializer_list>
 #include <memory>
 #include <utility>
 #include <ranges>
@@ -136,6 +137,47 @@ struct device_scratch_pool {
 inline device_scratch_pool &device_scratch() {
   static device_scratch_pool pool;
   return pool;
+}
+
+inline std::size_t align_up(std::size_t x) { return (x + 255) & ~std::size_t(255); }
+
+// A piece's slice of the device scratch as N fields in order, each rounded up
+// to 256 bytes (a field of 0 bytes takes no room): stated once, the slice's
+// size for carve_scratch and every field's pointer both come from it.
+template <std::size_t N> struct scratch_layout {
+  std::size_t off[N] = {}, bytes = 0;
+  scratch_layout() = default;
+  scratch_layout(std::initializer_list<std::size_t> field_bytes) {
+    std::size_t i = 0;
+    for (std::size_t b : field_bytes) {
+      off[i++] = bytes;
+      bytes += align_up(b);
+    }
+  }
+  template <typename T = char> T *at(char *base, std::size_t field) const {
+    return reinterpret_cast<T *>(base + off[field]);
+  }
+};
+
+// The device scratch of one algorithm call.  A call works on pieces (the
+// segments of its range; a distributed_span may list several of one rank) and
+// a rank has ONE cached block, so the call asks for the block once per rank,
+// sized for all of that rank's pieces, and every piece gets its own slice:
+// rank[k] and lay[k].bytes of piece k in, its base pointer out, the pieces of
+// a rank in piece order.  A second get() for the same rank could free the
+// block the first piece was given.
+template <std::size_t N>
+std::vector<char *> carve_scratch(const std::vector<std::size_t> &rank, const std::vector<scratch_layout<N>> &lay) {
+  std::vector<std::size_t> need(device_list().size(), 0);
+  for (std::size_t k = 0; k < rank.size(); k++) need.at(rank[k]) += lay[k].bytes;
+  std::vector<char *> next(need.size(), nullptr), base(rank.size());
+  for (std::size_t rk = 0; rk < need.size(); rk++)
+    if (need[rk]) next[rk] = static_cast<char *>(device_scratch().get(rk, need[rk]));
+  for (std::size_t k = 0; k < rank.size(); k++) {
+    base[k] = next[rank[k]];
+    next[rank[k]] += lay[k].bytes;
+  }
+  return base;
 }
 // The look-back scans' status buffers (dr/shp/scan.hpp "Epochs"): one per
 // segment, owned by the look-back scans alone (another user's bytes there

@@ -28,8 +28,9 @@
 //   1. every non-empty piece is scanned on its own segment stream, all pieces
 //      concurrently.  Where the piece's stretch of `out` lies in one segment of
 //      the piece's own rank it is written directly, with no extra pass;
-//      otherwise the piece goes through detail::device_scratch() and is copied
-//      out at the end, split at the output's segment boundaries;
+//      otherwise the piece goes through its slice of the segment's device
+//      scratch (detail::carve_scratch) and is copied out at the end, split at
+//      the output's segment boundaries (detail::out_cursor, select.hpp);
 //   2. a one-thread kernel behind it leaves the piece's edge record in pinned
 //      memory: first and last key, the index of the piece's first break (its
 //      size when the piece is one run) and the ACC fold of its last run, as
@@ -117,20 +118,6 @@ template <typename V, typename A, typename Op> __global__ void sbk_carry_kernel(
   if (i < m) out[i] = static_cast<V>(op(carry, static_cast<A>(out[i])));
 }
 
-// the position c elements further in osegs
-template <typename OSegs> void sbk_advance(const OSegs &osegs, std::size_t &oi, std::size_t &ooff, std::size_t c) {
-  while (c) {
-    if (ooff == osegs[oi].size()) {
-      oi++;
-      ooff = 0;
-      continue;
-    }
-    const std::size_t m = std::min(c, osegs[oi].size() - ooff);
-    ooff += m;
-    c -= m;
-  }
-}
-
 template <bool EXCL, typename KR, typename VR, typename OR, typename T, typename Eq, typename Op>
 void scan_by_key(const char *what, KR &&keys, VR &&values, OR &&out, T init_, Eq eq_, Op op_) {
   using namespace dr_segscan;
@@ -156,61 +143,43 @@ void scan_by_key(const char *what, KR &&keys, VR &&values, OR &&out, T init_, Eq
   const std::size_t total = static_cast<std::size_t>(std::ranges::size(keys));
   if (total != static_cast<std::size_t>(std::ranges::size(values)))
     throw std::invalid_argument(std::string(what) + ": keys and values differ in size");
-  if (vsegs.size() != P) throw std::invalid_argument(std::string(what) + ": keys and values are segmented differently");
-  for (std::size_t k = 0; k < P; k++)
-    if (ksegs[k].size() != vsegs[k].size() || ksegs[k].rank() != vsegs[k].rank())
-      throw std::invalid_argument(std::string(what) + ": keys and values are segmented differently");
-  for (auto &s : ksegs)
-    if (static_cast<unsigned long long>(s.size()) >= (1ull << 32))
-      throw std::length_error(std::string(what) + ": a piece of 2^32 elements or more on one segment");
+  check_segmented_alike(what, ksegs, vsegs);
+  check_piece_sizes(what, ksegs);
   if (total > static_cast<std::size_t>(std::ranges::size(out)))
     throw std::out_of_range(std::string(what) + ": " + std::to_string(total) + " elements, the output holds " +
                             std::to_string(std::ranges::size(out)));
 
   // per piece: where it is written (its stretch of `out`, or scratch), and its share of the segment's scratch:
   // [values of the piece, when it is not written directly | a copy of its input values, in-place exclusive | state]
+  using Cursor = out_cursor<decltype(osegs)>;
   struct piece {
     V *dst = nullptr; // direct
-    std::size_t oi = 0, ooff = 0;
+    Cursor at;        // where its stretch of `out` starts
     bool save = false;
-    std::size_t tv = 0, sv = 0, state = 0;
   };
-  std::vector<piece> lay(P);
-  std::vector<std::size_t> need(nprocs(), 0);
+  enum { TV, SV, STATE };
+  std::vector<piece> pc(P);
+  std::vector<scratch_layout<3>> lay(P);
+  std::vector<std::size_t> rank(P);
   {
-    std::size_t oi = 0, ooff = 0;
+    Cursor cur{&osegs};
     long first = -1;
     for (std::size_t k = 0; k < P; k++) {
       const std::size_t n = ksegs[k].size();
+      rank[k] = ksegs[k].rank();
       if (!n) continue;
-      while (ooff == osegs[oi].size()) { // the piece starts with the next output segment
-        oi++;
-        ooff = 0;
-      }
-      lay[k].oi = oi;
-      lay[k].ooff = ooff;
-      if (osegs[oi].size() - ooff >= n && osegs[oi].rank() == ksegs[k].rank()) lay[k].dst = static_cast<V *>(osegs[oi].data()) + ooff;
-      sbk_advance(osegs, oi, ooff, n);
-      std::size_t &b = need.at(ksegs[k].rank());
-      if (!lay[k].dst) {
-        lay[k].tv = b;
-        b += sel_round(n * sizeof(V));
-      }
-      if constexpr (EXCL && by_key_span_of<VSeg, V>()) {
-        if (first >= 0 && lay[k].dst == static_cast<const V *>(vsegs[k].data())) {
-          lay[k].save = true;
-          lay[k].sv = b;
-          b += sel_round(n * sizeof(V));
-        }
-      }
-      lay[k].state = b;
-      b += sel_round(ss_state_bytes_max<K, V>(n));
+      if (cur.room() >= n && cur.segment().rank() == rank[k]) pc[k].dst = static_cast<V *>(cur.next());
+      pc[k].at = cur;
+      cur.advance(n);
+      if constexpr (EXCL && by_key_span_of<VSeg, V>())
+        pc[k].save = first >= 0 && pc[k].dst == static_cast<const V *>(vsegs[k].data());
+      lay[k] = {pc[k].dst ? 0 : n * sizeof(V), pc[k].save ? n * sizeof(V) : 0, ss_state_bytes_max<K, V>(n)};
       if (first < 0) first = (long)k;
     }
   }
-  std::vector<char *> base(need.size(), nullptr);
-  for (std::size_t rk = 0; rk < need.size(); rk++)
-    if (need[rk]) base[rk] = static_cast<char *>(device_scratch().get(rk, need[rk]));
+  const std::vector<char *> base = carve_scratch(rank, lay);
+  // where piece k is scanned into: its stretch of `out`, or scratch
+  auto where = [&](std::size_t k) { return pc[k].dst ? pc[k].dst : lay[k].template at<V>(base[k], TV); };
 
   pinned<unsigned> err(1);
   err[0] = 0;
@@ -218,7 +187,7 @@ void scan_by_key(const char *what, KR &&keys, VR &&values, OR &&out, T init_, Eq
   auto launch = [&](std::size_t k, std::size_t m, V *o, A in, bool saved) {
     const std::size_t rk = ksegs[k].rank();
     hipStream_t st = stream(rk);
-    const ss_args a{base[rk] + lay[k].state, err.data()};
+    const ss_args a{lay[k].at(base[k], STATE), err.data()};
     auto go = [&](auto vin, auto vin_is_span) {
       if constexpr (by_key_span_of<KSeg, K>()) {
         const K *kp = static_cast<const K *>(ksegs[k].data());
@@ -233,7 +202,7 @@ void scan_by_key(const char *what, KR &&keys, VR &&values, OR &&out, T init_, Eq
           hip_check((ss_launch<K, V, A, false, EXCL>(st, accessor_of(ksegs[k]), vin, m, o, in, eq, op, a)), what);
       }
     };
-    if (saved) go(reinterpret_cast<const V *>(base[rk] + lay[k].sv), std::true_type{});
+    if (saved) go(lay[k].template at<const V>(base[k], SV), std::true_type{});
     else if constexpr (by_key_span_of<VSeg, V>()) go(static_cast<const V *>(vsegs[k].data()), std::true_type{});
     else go(accessor_of(vsegs[k]), std::false_type{});
   };
@@ -250,16 +219,15 @@ void scan_by_key(const char *what, KR &&keys, VR &&values, OR &&out, T init_, Eq
     const std::size_t rk = ksegs[k].rank();
     hipStream_t st = stream(rk);
     if constexpr (by_key_span_of<VSeg, V>()) {
-      if (lay[k].save)
-        hip_check(hipMemcpyAsync(base[rk] + lay[k].sv, static_cast<const V *>(vsegs[k].data()), n * sizeof(V),
+      if (pc[k].save)
+        hip_check(hipMemcpyAsync(lay[k].at(base[k], SV), static_cast<const V *>(vsegs[k].data()), n * sizeof(V),
                                  hipMemcpyDeviceToDevice, st),
                   "scan_by_key copy");
     }
-    V *o = lay[k].dst ? lay[k].dst : reinterpret_cast<V *>(base[rk] + lay[k].tv);
-    launch(k, n, o, init, false);
+    launch(k, n, where(k), init, false);
     auto kacc = accessor_of(ksegs[k]);
     hipLaunchKernelGGL((sbk_edge_kernel<K, A, decltype(kacc)>), dim3(1), dim3(1), 0, st, kacc, n,
-                       static_cast<const char *>(base[rk] + lay[k].state), &edge[k]);
+                       static_cast<const char *>(lay[k].at(base[k], STATE)), &edge[k]);
     hip_check(hipGetLastError(), "scan_by_key edge launch");
     if (first < 0) first = (long)k;
     else if (rk != ksegs[first].rank()) events.record(st);
@@ -267,7 +235,7 @@ void scan_by_key(const char *what, KR &&keys, VR &&values, OR &&out, T init_, Eq
   if (first < 0) return;
   {
     const std::size_t rk = ksegs[first].rank();
-    for (auto &e : events.ev) hip_check(hipStreamWaitEvent(stream(rk), e, 0), "hipStreamWaitEvent");
+    events.wait_on(stream(rk));
     hipLaunchKernelGGL((sbk_stitch_kernel<EXCL, K, A, by_key_eq<Eq>, by_key_op<A, Op>>), dim3(1), dim3(1), 0, stream(rk), edge.data(),
                        P, init, eq, op);
     hip_check(hipGetLastError(), "scan_by_key stitch launch");
@@ -279,21 +247,18 @@ void scan_by_key(const char *what, KR &&keys, VR &&values, OR &&out, T init_, Eq
     const std::size_t n = ksegs[k].size();
     if (!n) continue;
     const std::size_t rk = ksegs[k].rank();
-    V *o = lay[k].dst ? lay[k].dst : reinterpret_cast<V *>(base[rk] + lay[k].tv);
+    V *o = where(k);
     if (edge[k].has_carry) {
       const std::size_t m = static_cast<std::size_t>(edge[k].first_break);
       if constexpr (EXCL) {
-        launch(k, m, o, edge[k].xinit, lay[k].save);
+        launch(k, m, o, edge[k].xinit, pc[k].save);
       } else {
         hipLaunchKernelGGL((sbk_carry_kernel<V, A, by_key_op<A, Op>>), dim3((unsigned)((m + 255) / 256)), dim3(256), 0, stream(rk), o, m,
                            edge[k].carry, op);
         hip_check(hipGetLastError(), "scan_by_key carry launch");
       }
     }
-    if (!lay[k].dst) {
-      std::size_t oi = lay[k].oi, ooff = lay[k].ooff;
-      by_key_emit(osegs, oi, ooff, rk, static_cast<const V *>(o), n);
-    }
+    if (!pc[k].dst) pc[k].at.emit(rk, static_cast<const V *>(o), n);
   }
   select_sync(ksegs);
   select_check(err[0]);
@@ -325,7 +290,7 @@ OutputIter inclusive_scan_by_key(ExecutionPolicy &&policy, KIter kfirst, KIter k
   const std::size_t n = static_cast<std::size_t>(klast - kfirst);
   shp::inclusive_scan_by_key(std::forward<ExecutionPolicy>(policy), std::ranges::subrange(kfirst, klast),
                              std::ranges::subrange(vfirst, vfirst + static_cast<std::ptrdiff_t>(n)),
-                             detail::by_key_out(d_first, n), key_equal, op);
+                             detail::out_from(d_first, n), key_equal, op);
   return d_first + static_cast<std::ptrdiff_t>(n);
 }
 template <typename ExecutionPolicy, lib::distributed_iterator KIter, lib::distributed_iterator VIter,
@@ -335,7 +300,7 @@ OutputIter exclusive_scan_by_key(ExecutionPolicy &&policy, KIter kfirst, KIter k
   const std::size_t n = static_cast<std::size_t>(klast - kfirst);
   shp::exclusive_scan_by_key(std::forward<ExecutionPolicy>(policy), std::ranges::subrange(kfirst, klast),
                              std::ranges::subrange(vfirst, vfirst + static_cast<std::ptrdiff_t>(n)),
-                             detail::by_key_out(d_first, n), init, key_equal, op);
+                             detail::out_from(d_first, n), init, key_equal, op);
   return d_first + static_cast<std::ptrdiff_t>(n);
 }
 

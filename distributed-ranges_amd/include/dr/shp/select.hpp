@@ -18,14 +18,18 @@
 //
 // copy_if:
 //   1. every input piece is compacted on its own segment stream, all pieces
-//      concurrently, into that segment's detail::device_scratch(); its count
-//      goes to a pinned slot;
+//      concurrently, into its slice of that segment's device scratch
+//      (detail::carve_scratch); its count goes to a pinned slot;
 //   2. one wait; the host takes the exclusive prefix of the P counts;
 //   3. a total above size(out) throws std::out_of_range before anything is
 //      written to out;
 //   4. each compacted piece is copied into out with drhip_memcpy_d2d, split
 //      at output segment boundaries (peer copies when devices differ);
 //   5. sync.
+// The plumbing the by-key algorithms (reduce_by_key.hpp, scan_by_key.hpp)
+// share with copy_if is here too: the walk over output segments
+// (detail::out_cursor), the argument checks (check_piece_sizes,
+// check_segmented_alike) and the output of an iterator form (out_from).
 // One look-back pass and bulk copies; the temporary is as large as the piece
 // (DESIGN.md "Selection" has the alternative that avoids it).  A piece of
 // 2^32 elements or more throws std::length_error; an empty piece contributes
@@ -34,6 +38,7 @@
 
 #include <cstdint>
 #include <stdexcept>
+#include <string>
 #include <type_traits>
 #include <vector>
 
@@ -57,7 +62,6 @@ template <typename T> struct sel_equal_to {
 };
 
 constexpr unsigned kSelCountGrid = 512; // count_if's grid limit: 2 blocks per CU of a 256-CU device
-inline std::size_t sel_round(std::size_t b) { return (b + 255) & ~std::size_t(255); }
 
 // Enqueue the selection (MODE: a store variant) or the count (SEL_COUNT) of
 // the non-empty piece s on its segment's stream; `state` is device memory of
@@ -97,9 +101,69 @@ template <typename Segs> void select_sync(const Segs &segs) {
   for (auto rk : ranks) sync(rk);
 }
 
-template <typename Seg> void select_check_piece(const Seg &s) {
-  if (static_cast<unsigned long long>(s.size()) >= (1ull << 32))
-    throw std::length_error("shp: selection: a piece of 2^32 elements or more on one segment");
+// the kernels of this family index a piece with 32 bits
+template <typename Segs> void check_piece_sizes(const char *what, const Segs &segs) {
+  for (auto &s : segs)
+    if (static_cast<unsigned long long>(s.size()) >= (1ull << 32))
+      throw std::length_error(std::string(what) + ": a piece of 2^32 elements or more on one segment");
+}
+
+// a value travels beside its key: piece k of both on one rank, equally long
+template <typename KSegs, typename VSegs>
+void check_segmented_alike(const char *what, const KSegs &ksegs, const VSegs &vsegs) {
+  bool alike = ksegs.size() == vsegs.size();
+  for (std::size_t k = 0; alike && k < ksegs.size(); k++)
+    alike = ksegs[k].size() == vsegs[k].size() && ksegs[k].rank() == vsegs[k].rank();
+  if (!alike) throw std::invalid_argument(std::string(what) + ": keys and values are segmented differently");
+}
+
+// A position in a list of output segments (contiguous device spans).
+template <typename OSegs> struct out_cursor {
+  const OSegs *segs = nullptr;
+  std::size_t seg = 0, off = 0;
+  // the segment that holds the next element (exhausted and empty segments are passed over; an element must be left),
+  // the next element, and the room from it to that segment's end
+  const auto &segment() {
+    while (off == (*segs)[seg].size()) {
+      seg++;
+      off = 0;
+    }
+    return (*segs)[seg];
+  }
+  auto *next() { return segment().data() + off; }
+  std::size_t room() { return segment().size() - off; }
+  // the position c elements further
+  void advance(std::size_t c) {
+    walk(c, [](auto *, std::size_t) {});
+  }
+  // c elements of src (device memory of segment rank rk) to the position and past them, split at segment
+  // boundaries (peer copies when devices differ)
+  template <typename T> void emit(std::size_t rk, const T *src, std::size_t c) {
+    walk(c, [&](auto *dst, std::size_t m) {
+      check(drhip_memcpy_d2d(static_cast<int>(rk), dst, src, m * sizeof(T)), "drhip_memcpy_d2d");
+      src += m;
+    });
+  }
+  // the element passed last (after an advance or emit of c > 0)
+  auto *last() const { return (*segs)[seg].data() + (off - 1); }
+
+private:
+  template <typename F> void walk(std::size_t c, F &&f) {
+    while (c) {
+      const std::size_t m = std::min(c, room());
+      f(next(), m);
+      off += m;
+      c -= m;
+    }
+  }
+};
+
+// An output given by its first iterator: it has room for at most n elements
+// and is taken to end with the iterator's container if that comes sooner.
+template <typename OutputIter> auto out_from(OutputIter d_first, std::size_t n) {
+  std::size_t room = 0;
+  for (auto &s : d_first.segments()) room += s.size();
+  return std::ranges::subrange(d_first, d_first + static_cast<std::ptrdiff_t>(std::min(room, n)));
 }
 
 } // namespace detail
@@ -111,7 +175,7 @@ std::size_t count_if(ExecutionPolicy &&, R &&r, Pred pred) {
   using Seg = std::remove_cvref_t<decltype(segs[0])>;
   using V = typename decltype(detail::value_type_of_segment<Seg>())::type;
   const std::size_t P = segs.size();
-  for (auto &s : segs) detail::select_check_piece(s);
+  detail::check_piece_sizes("shp: selection", segs);
   detail::pinned<unsigned long long> cnt(P);
   detail::pinned<unsigned> err(1);
   err[0] = 0;
@@ -148,26 +212,18 @@ auto copy_if(ExecutionPolicy &&, R &&r, O &&out, Pred pred) {
                 "shp::copy_if: the output's value type must be the input's");
   static_assert(std::is_trivially_copyable_v<V>, "shp::copy_if: elements move as bits");
   const std::size_t P = segs.size();
-  for (auto &s : segs) detail::select_check_piece(s);
+  detail::check_piece_sizes("shp: selection", segs);
 
-  // per segment: [compacted piece | status words] for each of its pieces
-  struct piece {
-    std::size_t tmp = 0, state = 0;
-  };
-  std::vector<piece> lay(P);
-  std::vector<std::size_t> need(nprocs(), 0);
+  // per non-empty piece: [compacted piece | status words]
+  enum { TMP, STATE };
+  std::vector<detail::scratch_layout<2>> lay(P);
+  std::vector<std::size_t> rank(P);
   for (std::size_t k = 0; k < P; k++) {
     const std::size_t n = segs[k].size();
-    if (!n) continue;
-    std::size_t &b = need.at(segs[k].rank());
-    lay[k].tmp = b;
-    b += detail::sel_round(n * sizeof(V));
-    lay[k].state = b;
-    b += detail::sel_round(dr_select::sel_state_bytes<V>(n));
+    rank[k] = segs[k].rank();
+    if (n) lay[k] = {n * sizeof(V), dr_select::sel_state_bytes<V>(n)};
   }
-  std::vector<char *> base(need.size(), nullptr);
-  for (std::size_t rk = 0; rk < need.size(); rk++)
-    if (need[rk]) base[rk] = static_cast<char *>(detail::device_scratch().get(rk, need[rk]));
+  const std::vector<char *> base = detail::carve_scratch(rank, lay);
 
   detail::pinned<unsigned long long> cnt(P);
   detail::pinned<unsigned> err(1);
@@ -175,9 +231,8 @@ auto copy_if(ExecutionPolicy &&, R &&r, O &&out, Pred pred) {
   for (std::size_t k = 0; k < P; k++) {
     cnt[k] = 0;
     if (!segs[k].size()) continue;
-    char *b = base[segs[k].rank()];
-    detail::select_launch<V, dr_select::kSelMode>(segs[k], reinterpret_cast<V *>(b + lay[k].tmp), pred,
-                                                  b + lay[k].state, &cnt[k], err.data());
+    detail::select_launch<V, dr_select::kSelMode>(segs[k], lay[k].template at<V>(base[k], TMP), pred,
+                                                  lay[k].at(base[k], STATE), &cnt[k], err.data());
   }
   detail::select_sync(segs);
   detail::select_check(err[0]);
@@ -189,25 +244,9 @@ auto copy_if(ExecutionPolicy &&, R &&r, O &&out, Pred pred) {
                             std::to_string(std::ranges::size(out)));
 
   // the compacted pieces, in order, into the output's segments
-  std::size_t oi = 0, ooff = 0;
-  for (std::size_t k = 0; k < P; k++) {
-    std::size_t c = static_cast<std::size_t>(cnt[k]);
-    if (!c) continue;
-    const V *src = reinterpret_cast<const V *>(base[segs[k].rank()] + lay[k].tmp);
-    while (c) {
-      if (ooff == osegs[oi].size()) {
-        oi++;
-        ooff = 0;
-        continue;
-      }
-      const std::size_t m = std::min(c, osegs[oi].size() - ooff);
-      detail::check(drhip_memcpy_d2d(static_cast<int>(segs[k].rank()), osegs[oi].data() + ooff, src, m * sizeof(V)),
-                    "drhip_memcpy_d2d");
-      src += m;
-      ooff += m;
-      c -= m;
-    }
-  }
+  detail::out_cursor<decltype(osegs)> cur{&osegs};
+  for (std::size_t k = 0; k < P; k++)
+    if (cnt[k]) cur.emit(segs[k].rank(), lay[k].template at<const V>(base[k], TMP), static_cast<std::size_t>(cnt[k]));
   detail::select_sync(segs);
   return std::ranges::begin(out) + static_cast<std::ranges::range_difference_t<O>>(total);
 }
@@ -222,15 +261,11 @@ std::size_t count(ExecutionPolicy &&policy, Iter first, Iter last, const T &valu
   return shp::count(std::forward<ExecutionPolicy>(policy), std::ranges::subrange(first, last), value);
 }
 // std::copy_if's form: the output starts at d_first and has room for the
-// elements selected (at most last - first are written; the output is taken
-// to end with d_first's container if that comes sooner)
+// elements selected (at most last - first are written)
 template <typename ExecutionPolicy, lib::distributed_iterator Iter, lib::distributed_iterator OutputIter, typename Pred>
 OutputIter copy_if(ExecutionPolicy &&policy, Iter first, Iter last, OutputIter d_first, Pred pred) {
-  std::size_t room = 0;
-  for (auto &s : d_first.segments()) room += s.size();
-  const std::size_t len = std::min(room, static_cast<std::size_t>(last - first));
   return shp::copy_if(std::forward<ExecutionPolicy>(policy), std::ranges::subrange(first, last),
-                      std::ranges::subrange(d_first, d_first + static_cast<std::ptrdiff_t>(len)), pred);
+                      detail::out_from(d_first, static_cast<std::size_t>(last - first)), pred);
 }
 
 } // namespace shp

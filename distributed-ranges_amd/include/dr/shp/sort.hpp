@@ -14,19 +14,27 @@
 //      step (the same code dr_dist.exact_splits runs over two allgathers);
 //   3. every (source, destination) piece moves with one device-to-device
 //      copy (xGMI peer copy across GPUs) into a per-destination buffer;
-//   4. every destination merges its P sorted runs (drhip_merge_runs) and
-//      copies them back into its segment.
-// All device scratch comes from the cached per-segment pool.  With P == 1
-// only step 1's sort runs.  shp::sort_by_key (at the end of this file)
-// takes the same four steps with a value carried beside every key.
+//   4. every destination merges its P sorted runs straight into its segment
+//      (drhip_merge_runs_to).
+// All device scratch comes from the cached per-segment pool
+// (detail::carve_scratch, runtime.hpp).  With P == 1 only step 1's sort runs.
+// shp::sort_by_key (at the end of this file) takes the same four steps with a
+// value carried beside every key, and the comparator tier (detail::
+// sort_general) with its own local sort, splitting and merge.  What the three
+// share is written once: the sample plan and the run offsets in dr/details/
+// split_plan.hpp, and in detail below the non-empty parts (nonempty_parts),
+// the two host gathers of step 2 (gather_samples, gather_windows) and step 3
+// (move_pieces); each tier keeps its own sort, split and merge calls.
 #pragma once
 
 #include <cstring>
 #include <functional>
-#include <map>
+#include <initializer_list>
+#include <string>
 
 #include "algorithms.hpp"
 #include "merge_sort.hpp"
+#include "select.hpp"
 #include "../details/split_plan.hpp"
 
 namespace shp {
@@ -83,131 +91,161 @@ template <> struct key_bits<double> {
   }
 };
 
-// Per-segment scratch of one sort call, carved from the cached per-rank
-// device scratch (runtime.hpp device_scratch: grown once, reused by later
-// calls, released by finalize) -- the sort allocates nothing per call once
-// warm.  Layout per segment: [radix workspace | n-key exchange buffer |
-// merge workspace | regular samples].  Segments that share a rank (a
-// distributed_span may list several segments of one rank) get disjoint
-// slices of that rank's ONE scratch block, sized for all of them.
-// sort_by_key adds the value exchange buffer (vbuf, after buf) and sizes ws /
-// mws by the pairs workspaces.
-struct sort_scratch {
-  void *ws = nullptr, *buf = nullptr, *vbuf = nullptr, *mws = nullptr, *smp = nullptr;
-  std::size_t wsb = 0, mwsb = 0, bytes = 0;
+// Per-segment scratch of one sort call, from the cached per-rank device
+// scratch (runtime.hpp device_scratch: grown once, reused by later calls,
+// released by finalize) -- the sort allocates nothing per call once warm.
+// Per segment of the radix tiers: [radix workspace | n-key exchange buffer |
+// n-value exchange buffer | merge workspace | regular samples of the keys].
+// Everything after the workspace serves the exchange between segments (P > 1);
+// shp::sort carries no values (vb == 0).
+enum { SORT_WS, SORT_BUF, SORT_VBUF, SORT_MWS, SORT_SMP };
+using sort_layout = scratch_layout<5>;
+template <typename T>
+sort_layout radix_sort_layout(std::size_t wsb, std::size_t mwsb, std::size_t n, std::size_t vb, std::size_t nsamples,
+                              std::size_t P) {
+  if (P == 1) return {wsb, 0, 0, 0, 0};
+  return {wsb, n * sizeof(T), n * vb, mwsb, nsamples * sizeof(T)};
+}
+
+// The non-empty segments of a range, their sizes and ranks, and the plan of
+// every segment's regular samples (dr_plan::plan_samples).
+template <typename T> struct sort_parts {
+  std::vector<device_span<T>> parts;
+  std::vector<std::uint64_t> n, stride, ns;
+  std::vector<std::size_t> rank;
+  std::size_t size() const { return parts.size(); }
+  const device_span<T> &operator[](std::size_t k) const { return parts[k]; }
 };
-
-inline std::size_t align_up(std::size_t x) { return (x + 255) & ~std::size_t(255); }
-
-template <typename T>
-sort_scratch size_sort_scratch(std::size_t rank, std::size_t n, std::size_t P, std::size_t nsamples) {
-  const int r = static_cast<int>(rank);
-  sort_scratch sc;
-  check(drhip_sort_workspace(r, dtype_code<T>(), n, &sc.wsb), "drhip_sort_workspace");
-  if (P > 1) check(drhip_merge_workspace(r, dtype_code<T>(), n, static_cast<int>(P), &sc.mwsb), "drhip_merge_workspace");
-  const std::size_t bufb = P > 1 ? align_up(n * sizeof(T)) : 0;
-  const std::size_t smpb = P > 1 ? align_up(nsamples * sizeof(T)) : 0;
-  sc.bytes = align_up(sc.wsb) + bufb + align_up(sc.mwsb) + smpb;
-  return sc;
+template <typename T, typename Segs> sort_parts<T> nonempty_parts(Segs &&segs) {
+  sort_parts<T> z;
+  for (auto &&s : segs) {
+    if (!s.size()) continue;
+    const dr_plan::sample_plan sp = dr_plan::plan_samples(s.size());
+    z.parts.push_back(s);
+    z.n.push_back(s.size());
+    z.stride.push_back(sp.stride);
+    z.ns.push_back(sp.ns);
+    z.rank.push_back(s.rank());
+  }
+  return z;
 }
 
-template <typename T> void carve_sort_scratch(sort_scratch &sc, char *base, std::size_t n, std::size_t P) {
-  const std::size_t bufb = P > 1 ? align_up(n * sizeof(T)) : 0;
-  sc.ws = base;
-  sc.buf = base + align_up(sc.wsb);
-  sc.mws = base + align_up(sc.wsb) + bufb;
-  sc.smp = base + align_up(sc.wsb) + bufb + align_up(sc.mwsb);
+// Step 1b: the ns[k] samples at smp[k] (device memory of part k) to the host,
+// part after part; hs has room for the sum of ns.
+template <typename T> void gather_samples(const sort_parts<T> &z, const std::vector<T *> &smp, T *hs) {
+  for (std::size_t k = 0; k < z.size(); hs += z.ns[k], k++)
+    check(drhip_memcpy_d2h(static_cast<int>(z.rank[k]), hs, smp[k], z.ns[k] * sizeof(T)), "sort samples d2h");
+  for (std::size_t k = 0; k < z.size(); k++) sync(z.rank[k]);
 }
 
-// The same for sort_by_key with values of vb bytes: [pairs radix workspace |
-// n-key exchange buffer | n-value exchange buffer | pairs merge workspace |
-// regular samples of the keys].
-template <typename T>
-sort_scratch size_pairs_scratch(std::size_t rank, std::size_t n, std::size_t P, std::size_t nsamples, std::size_t vb) {
-  const int r = static_cast<int>(rank);
-  sort_scratch sc;
-  check(drhip_sort_pairs_workspace(r, dtype_code<T>(), vb, n, &sc.wsb), "drhip_sort_pairs_workspace");
-  if (P > 1)
-    check(drhip_merge_pairs_workspace(r, dtype_code<T>(), vb, n, static_cast<int>(P), &sc.mwsb),
-          "drhip_merge_pairs_workspace");
-  const std::size_t bufb = P > 1 ? align_up(n * sizeof(T)) + align_up(n * vb) : 0;
-  const std::size_t smpb = P > 1 ? align_up(nsamples * sizeof(T)) : 0;
-  sc.bytes = align_up(sc.wsb) + bufb + align_up(sc.mwsb) + smpb;
-  return sc;
+// Step 2b: the windows of the split (win[2 (s nb + k) + {0, 1}] = the slice of
+// part s that holds boundary k's bracket) to the host, in (part, boundary)
+// order; hw has room for window_total(win).
+inline std::size_t window_total(const std::vector<std::uint64_t> &win) {
+  std::size_t t = 0;
+  for (std::size_t i = 0; i < win.size(); i += 2) t += win[i + 1] - win[i];
+  return t;
+}
+template <typename T> void gather_windows(const sort_parts<T> &z, const std::vector<std::uint64_t> &win, T *hw) {
+  const std::size_t nb = z.size() - 1;
+  for (std::size_t s = 0; s < z.size(); s++)
+    for (std::size_t k = 0; k < nb; k++) {
+      const std::size_t a = win[2 * (s * nb + k)], b = win[2 * (s * nb + k) + 1];
+      if (b > a)
+        check(drhip_memcpy_d2h(static_cast<int>(z.rank[s]), hw, z[s].data() + a, (b - a) * sizeof(T)),
+              "sort slices d2h");
+      hw += b - a;
+    }
+  for (std::size_t s = 0; s < z.size(); s++) sync(z.rank[s]);
 }
 
-template <typename T> void carve_pairs_scratch(sort_scratch &sc, char *base, std::size_t n, std::size_t P, std::size_t vb) {
-  const std::size_t kbufb = P > 1 ? align_up(n * sizeof(T)) : 0, vbufb = P > 1 ? align_up(n * vb) : 0;
-  sc.ws = base;
-  sc.buf = base + align_up(sc.wsb);
-  sc.vbuf = base + align_up(sc.wsb) + kbufb;
-  sc.mws = base + align_up(sc.wsb) + kbufb + vbufb;
-  sc.smp = base + align_up(sc.wsb) + kbufb + vbufb + align_up(sc.mwsb);
+// the boundary ranks of the split: g[k] = the sizes of the segments <= k
+inline std::vector<std::uint64_t> boundary_ranks(const std::vector<std::uint64_t> &n) {
+  std::vector<std::uint64_t> g(n.size() - 1);
+  for (std::size_t k = 0, acc = 0; k < g.size(); k++) g[k] = acc += n[k];
+  return g;
 }
 
-// Regular samples per segment for the exact splitting (split.hip): a stride
-// of ceil(n / kSortSamples) keys keeps every boundary's bracket to a few
-// strides of keys per segment.
-constexpr std::size_t kSortSamples = std::size_t(1) << 16;
-
-} // namespace detail
-
-namespace detail {
-
-// Steps 1b-2 of the distributed sort, on keys alone (shared by shp::sort and
+// Steps 1b-2 of the radix tiers, on keys alone (shared by shp::sort and
 // shp::sort_by_key): the regular samples of every locally sorted segment
-// come to the host, then the exact splitting at the segment boundaries.
-// Needs P > 1.  Returns split[s * P + k] = the number of segment s's keys that go to
+// come to the host, then the exact splitting at the segment boundaries
+// (csrc/split.hip): value brackets from the samples, then each boundary key
+// on the slices of every sorted segment that hold its bracket.  Needs P > 1.
+// Returns split[s * P + k] = the number of segment s's keys that go to
 // destinations <= k; keys equal to a boundary key are given out in segment
 // order, which is what keeps sort_by_key stable across segments.
-template <typename T>
-std::vector<std::uint64_t> exact_splits(const std::vector<device_span<T>> &parts, const std::vector<sort_scratch> &sc,
-                                        const std::vector<std::uint64_t> &n, const std::vector<std::uint64_t> &stride,
-                                        const std::vector<std::uint64_t> &ns) {
+template <typename T> std::vector<std::uint64_t> exact_splits(const sort_parts<T> &z, const std::vector<T *> &smp) {
   using KB = key_bits<T>;
-  const std::size_t P = parts.size(), nb = P - 1;
+  const std::size_t P = z.size(), nb = P - 1;
+  auto bits_of = [](const T *h, std::size_t count) {
+    std::vector<std::uint64_t> bits(count);
+    for (std::size_t i = 0; i < count; i++) bits[i] = static_cast<std::uint64_t>(KB::in(h[i]));
+    return bits;
+  };
   std::size_t tot_smp = 0;
-  for (auto v : ns) tot_smp += v;
+  for (auto v : z.ns) tot_smp += v;
   pinned<T> hs(tot_smp);
-  for (std::size_t k = 0, off = 0; k < P; off += ns[k], k++)
-    check(drhip_memcpy_d2h(static_cast<int>(parts[k].rank()), hs.data() + off, sc[k].smp, ns[k] * sizeof(T)),
-          "sort samples d2h");
-  for (std::size_t k = 0; k < P; k++) sync(parts[k].rank());
-
-  // 2. exact splitting at the segment boundaries (csrc/split.hip): value
-  //    brackets from the samples, then each boundary key on the slices of
-  //    every sorted segment that hold its bracket
-  std::vector<std::uint64_t> g(nb), lo(nb), hi(nb), win(2 * P * nb), split(P * (nb + 1));
-  for (std::size_t k = 0, acc = 0; k < nb; k++) g[k] = acc += n[k];
-  {
-    std::vector<std::uint64_t> bits(tot_smp);
-    for (std::size_t i = 0; i < tot_smp; i++) bits[i] = static_cast<std::uint64_t>(KB::in(hs[i]));
-    check(drhip_split_windows(static_cast<int>(P), n.data(), stride.data(), ns.data(), bits.data(),
-                              static_cast<int>(nb), g.data(), lo.data(), hi.data(), win.data()),
-          "drhip_split_windows");
-  }
-  std::size_t tot_win = 0;
-  for (std::size_t i = 0; i < P * nb; i++) tot_win += win[2 * i + 1] - win[2 * i];
-  {
-    pinned<T> hw(tot_win);
-    std::size_t off = 0;
-    for (std::size_t s = 0; s < P; s++)
-      for (std::size_t k = 0; k < nb; k++) {
-        const std::size_t a = win[2 * (s * nb + k)], b = win[2 * (s * nb + k) + 1];
-        if (b > a)
-          check(drhip_memcpy_d2h(static_cast<int>(parts[s].rank()), hw.data() + off, parts[s].data() + a,
-                                 (b - a) * sizeof(T)),
-                "sort slices d2h");
-        off += b - a;
-      }
-    for (std::size_t s = 0; s < P; s++) sync(parts[s].rank());
-    std::vector<std::uint64_t> wbits(tot_win);
-    for (std::size_t i = 0; i < tot_win; i++) wbits[i] = static_cast<std::uint64_t>(KB::in(hw[i]));
-    check(drhip_split_exact(static_cast<int>(P), n.data(), static_cast<int>(nb), g.data(), lo.data(), hi.data(),
-                            win.data(), wbits.data(), split.data()),
-          "drhip_split_exact");
-  }
+  gather_samples(z, smp, hs.data());
+  const std::vector<std::uint64_t> g = boundary_ranks(z.n);
+  std::vector<std::uint64_t> lo(nb), hi(nb), win(2 * P * nb), split(P * (nb + 1));
+  check(drhip_split_windows(static_cast<int>(P), z.n.data(), z.stride.data(), z.ns.data(),
+                            bits_of(hs.data(), tot_smp).data(), static_cast<int>(nb), g.data(), lo.data(), hi.data(),
+                            win.data()),
+        "drhip_split_windows");
+  const std::size_t tot_win = window_total(win);
+  pinned<T> hw(tot_win);
+  gather_windows(z, win, hw.data());
+  check(drhip_split_exact(static_cast<int>(P), z.n.data(), static_cast<int>(nb), g.data(), lo.data(), hi.data(),
+                          win.data(), bits_of(hw.data(), tot_win).data(), split.data()),
+        "drhip_split_exact");
   return split;
+}
+
+// One lane of step 3: src[s] is source s's data, dst[k] destination k's
+// exchange buffer, elements of `elem` bytes.  sort_by_key moves a key lane and
+// a value lane by the same split indices.
+struct sort_lane {
+  std::vector<const char *> src;
+  std::vector<char *> dst;
+  std::size_t elem;
+  const char *what;
+};
+template <typename T>
+sort_lane make_lane(const std::vector<device_span<T>> &parts, const std::vector<T *> &bufs, const char *what) {
+  sort_lane l{{}, {}, sizeof(T), what};
+  for (std::size_t k = 0; k < parts.size(); k++) {
+    l.src.push_back(reinterpret_cast<const char *>(parts[k].data()));
+    l.dst.push_back(reinterpret_cast<char *>(bufs[k]));
+  }
+  return l;
+}
+
+// Step 3: every (source s, destination k) piece, source s's range
+// [split[s][k-1], split[s][k]), moves with one device-to-device copy per lane
+// (xGMI peer copy across GPUs) to its run offset in destination k's buffer, the
+// runs in source order.  Returns every destination's run offsets for the
+// merge; waits for the copies (they read the segments the merge writes).
+inline std::vector<std::vector<std::size_t>> move_pieces(const char *who, const std::vector<std::size_t> &rank,
+                                                          const std::vector<std::uint64_t> &n,
+                                                          const std::vector<std::uint64_t> &split,
+                                                          std::initializer_list<sort_lane> lanes) {
+  const int P = static_cast<int>(n.size());
+  std::vector<std::vector<std::size_t>> offs(P);
+  for (int k = 0; k < P; k++) {
+    dr_plan::run_plan r = dr_plan::plan_runs(split.data(), P, P, k);
+    for (int s = 0; s < P; s++) {
+      const std::size_t a = r.from[s], b = a + (r.offs[s + 1] - r.offs[s]); // source s's range
+      if (b > a)
+        for (const sort_lane &l : lanes)
+          check(drhip_memcpy_d2d(static_cast<int>(rank[k]), l.dst[k] + r.offs[s] * l.elem, l.src[s] + a * l.elem,
+                                 (b - a) * l.elem),
+                l.what);
+    }
+    if (r.offs[P] != n[k]) throw std::runtime_error(std::string(who) + ": splitting did not balance");
+    offs[k] = std::move(r.offs);
+  }
+  sync_all();
+  return offs;
 }
 
 } // namespace detail
@@ -228,78 +266,49 @@ void sort(ExecutionPolicy &&, R &&r) {
     detail::sort_general<T>(segs, std::less<>{});
     return;
   } else {
-  std::vector<device_span<T>> parts;
-  for (auto &s : segs)
-    if (s.size()) parts.push_back(s);
-  const std::size_t P = parts.size();
+  const auto z = detail::nonempty_parts<T>(segs);
+  const std::size_t P = z.size();
   if (P == 0) return;
-  std::vector<std::uint64_t> n(P), stride(P), ns(P);
+  const int dt = detail::dtype_code<T>();
+  std::vector<std::size_t> wsb(P), mwsb(P, 0);
+  std::vector<detail::sort_layout> lay(P);
   for (std::size_t k = 0; k < P; k++) {
-    n[k] = parts[k].size();
-    stride[k] = std::max<std::uint64_t>(1, (n[k] + detail::kSortSamples - 1) / detail::kSortSamples);
-    ns[k] = (n[k] + stride[k] - 1) / stride[k];
+    const int rk = static_cast<int>(z.rank[k]);
+    detail::check(drhip_sort_workspace(rk, dt, z.n[k], &wsb[k]), "drhip_sort_workspace");
+    if (P > 1)
+      detail::check(drhip_merge_workspace(rk, dt, z.n[k], static_cast<int>(P), &mwsb[k]), "drhip_merge_workspace");
+    lay[k] = detail::radix_sort_layout<T>(wsb[k], mwsb[k], z.n[k], 0, z.ns[k], P);
   }
-  std::vector<detail::sort_scratch> sc(P);
-  {
-    std::map<std::size_t, std::size_t> rank_bytes; // one scratch block per rank, carved per segment
-    for (std::size_t k = 0; k < P; k++) {
-      sc[k] = detail::size_sort_scratch<T>(parts[k].rank(), n[k], P, ns[k]);
-      rank_bytes[parts[k].rank()] += sc[k].bytes;
-    }
-    std::map<std::size_t, char *> rank_next;
-    for (auto &[rk, b] : rank_bytes) rank_next[rk] = static_cast<char *>(detail::device_scratch().get(rk, b));
-    for (std::size_t k = 0; k < P; k++) {
-      char *&next = rank_next[parts[k].rank()];
-      detail::carve_sort_scratch<T>(sc[k], next, n[k], P);
-      next += sc[k].bytes;
-    }
+  const std::vector<char *> base = detail::carve_scratch(z.rank, lay);
+  std::vector<T *> buf(P), smp(P);
+  for (std::size_t k = 0; k < P; k++) {
+    buf[k] = lay[k].template at<T>(base[k], detail::SORT_BUF);
+    smp[k] = lay[k].template at<T>(base[k], detail::SORT_SMP);
   }
 
   // 1. local sorts (every segment in flight), then the regular samples
   for (std::size_t k = 0; k < P; k++) {
-    const int rk = static_cast<int>(parts[k].rank());
-    if (n[k] > 1)
-      detail::check(drhip_sort(rk, detail::dtype_code<T>(), parts[k].data(), n[k], sc[k].ws, sc[k].wsb), "drhip_sort");
-    if (P > 1)
-      detail::check(drhip_sort_sample(rk, detail::dtype_code<T>(), parts[k].data(), n[k], stride[k], sc[k].smp),
-                    "drhip_sort_sample");
+    const int rk = static_cast<int>(z.rank[k]);
+    if (z.n[k] > 1)
+      detail::check(drhip_sort(rk, dt, z[k].data(), z.n[k], lay[k].at(base[k], detail::SORT_WS), wsb[k]), "drhip_sort");
+    if (P > 1) detail::check(drhip_sort_sample(rk, dt, z[k].data(), z.n[k], z.stride[k], smp[k]), "drhip_sort_sample");
   }
   if (P == 1) {
-    sync(parts[0].rank());
+    sync(z.rank[0]);
     return;
   }
   // 2. exact splitting at the segment boundaries
-  const std::size_t nb = P - 1;
-  const std::vector<std::uint64_t> split = detail::exact_splits<T>(parts, sc, n, stride, ns);
-  auto sp = [&](std::size_t s, std::size_t k) -> std::size_t { return split[s * (nb + 1) + k]; };
-
-  // 3. move pieces: source s range [split[s][k-1], split[s][k]) -> dest k
-  //    (xGMI peer copies across GPUs)
-  for (std::size_t k = 0; k < P; k++) {
-    std::size_t off = 0;
-    for (std::size_t s = 0; s < P; s++) {
-      const std::size_t a = k == 0 ? 0 : sp(s, k - 1), b = sp(s, k);
-      if (b > a)
-        detail::check(drhip_memcpy_d2d(static_cast<int>(parts[k].rank()), static_cast<T *>(sc[k].buf) + off,
-                                       parts[s].data() + a, (b - a) * sizeof(T)),
-                      "sort piece copy");
-      off += b - a;
-    }
-    if (off != n[k]) throw std::runtime_error("shp::sort: splitting did not balance");
-  }
-  sync_all();
+  const std::vector<std::uint64_t> split = detail::exact_splits<T>(z, smp);
+  // 3. move pieces
+  const auto offs =
+      detail::move_pieces("shp::sort", z.rank, z.n, split, {detail::make_lane(z.parts, buf, "sort piece copy")});
   // 4. destination merge of the P sorted runs straight into the segment
   //    (drhip_merge_runs_to: ceil(log2 P) merge-path passes instead of a
-  //    second radix sort, the last pass writing the segment -- no copy back;
-  //    every piece copy of step 3 has finished reading the segments)
-  for (std::size_t k = 0; k < P; k++) {
-    const int rk = static_cast<int>(parts[k].rank());
-    std::vector<std::size_t> offs(P + 1, 0);
-    for (std::size_t s = 0; s < P; s++) offs[s + 1] = offs[s] + (sp(s, k) - (k == 0 ? 0 : sp(s, k - 1)));
-    detail::check(drhip_merge_runs_to(rk, detail::dtype_code<T>(), sc[k].buf, parts[k].data(), n[k], offs.data(),
-                                      static_cast<int>(P), sc[k].mws, sc[k].mwsb),
+  //    second radix sort, the last pass writing the segment -- no copy back)
+  for (std::size_t k = 0; k < P; k++)
+    detail::check(drhip_merge_runs_to(static_cast<int>(z.rank[k]), dt, buf[k], z[k].data(), z.n[k], offs[k].data(),
+                                      static_cast<int>(P), lay[k].at(base[k], detail::SORT_MWS), mwsb[k]),
                   "drhip_merge_runs_to");
-  }
   sync_all();
   }
 }
@@ -347,104 +356,64 @@ namespace detail {
 template <typename T, typename Comp> void sort_general(auto &segs, Comp comp) {
   static_assert(std::is_trivially_copyable_v<T>, "shp::sort: the element type must be trivially copyable");
   static_assert(sizeof(T) <= 256, "shp::sort: elements above 256 bytes are not supported");
-  std::vector<device_span<T>> parts;
-  for (auto &s : segs)
-    if (s.size()) parts.push_back(s);
-  const std::size_t P = parts.size();
+  const auto z = nonempty_parts<T>(segs);
+  const std::size_t P = z.size();
   if (P == 0) return;
-  std::vector<std::uint64_t> n(P), stride(P), ns(P);
-  for (std::size_t k = 0; k < P; k++) {
-    n[k] = parts[k].size();
-    stride[k] = std::max<std::uint64_t>(1, (n[k] + kSortSamples - 1) / kSortSamples);
-    ns[k] = P > 1 ? (n[k] + stride[k] - 1) / stride[k] : 0;
-  }
+  const std::vector<std::uint64_t> &n = z.n;
   // per segment: [local-sort scratch (doubles as the piece buffer) | samples]
-  auto seg_bytes = [&](std::size_t k) { return align_up(msort::scratch_bytes<T>(n[k])) + align_up(ns[k] * sizeof(T)); };
-  std::vector<char *> base(P);
-  {
-    std::map<std::size_t, std::size_t> rank_bytes;
-    for (std::size_t k = 0; k < P; k++) rank_bytes[parts[k].rank()] += seg_bytes(k);
-    std::map<std::size_t, char *> next;
-    for (auto &[rk, b] : rank_bytes) next[rk] = static_cast<char *>(device_scratch().get(rk, b));
-    for (std::size_t k = 0; k < P; k++) {
-      base[k] = next[parts[k].rank()];
-      next[parts[k].rank()] += seg_bytes(k);
-    }
+  enum { BUF, SMP };
+  std::vector<scratch_layout<2>> lay(P);
+  for (std::size_t k = 0; k < P; k++) lay[k] = {msort::scratch_bytes<T>(n[k]), P > 1 ? z.ns[k] * sizeof(T) : 0};
+  const std::vector<char *> base = carve_scratch(z.rank, lay);
+  std::vector<T *> buf(P), smp(P);
+  for (std::size_t k = 0; k < P; k++) {
+    buf[k] = lay[k].template at<T>(base[k], BUF);
+    smp[k] = lay[k].template at<T>(base[k], SMP);
   }
-  auto smp = [&](std::size_t k) { return reinterpret_cast<T *>(base[k] + align_up(msort::scratch_bytes<T>(n[k]))); };
   auto st = [&](std::size_t k) {
-    hip_check(hipSetDevice(device_list().at(parts[k].rank())), "hipSetDevice");
-    return stream(parts[k].rank());
+    hip_check(hipSetDevice(device_list().at(z.rank[k])), "hipSetDevice");
+    return stream(z.rank[k]);
   };
   // 1. local sorts and samples
   for (std::size_t k = 0; k < P; k++) {
     hipStream_t s = st(k);
-    msort::local_sort(parts[k].data(), n[k], base[k], comp, s);
+    msort::local_sort(z[k].data(), n[k], base[k], comp, s);
     if (P > 1)
-      hipLaunchKernelGGL((msort::gather_samples_kernel<T>), dim3(msort::blocks_of(ns[k], 256)), dim3(256), 0, s,
-                         parts[k].data(), stride[k], ns[k], smp(k));
+      hipLaunchKernelGGL((msort::gather_samples_kernel<T>), dim3(msort::blocks_of(z.ns[k], 256)), dim3(256), 0, s,
+                         z[k].data(), z.stride[k], z.ns[k], smp[k]);
     hip_check(hipGetLastError(), "shp::sort launch");
   }
   if (P == 1) {
-    sync(parts[0].rank());
+    sync(z.rank[0]);
     return;
   }
-  std::size_t tot_smp = 0;
-  for (auto v : ns) tot_smp += v;
-  std::vector<T> hs(tot_smp);
-  for (std::size_t k = 0, off = 0; k < P; off += ns[k], k++)
-    check(drhip_memcpy_d2h(static_cast<int>(parts[k].rank()), hs.data() + off, smp(k), ns[k] * sizeof(T)),
-          "sort samples d2h");
-  for (std::size_t k = 0; k < P; k++) sync(parts[k].rank());
   // 2. exact splitting under comp
   const std::size_t nb = P - 1;
-  std::vector<std::uint64_t> g(nb), win(2 * P * nb), split(P * (nb + 1));
-  for (std::size_t k = 0, acc = 0; k < nb; k++) g[k] = acc += n[k];
-  if (const char *why = dr_plan::split_windows_cmp(static_cast<int>(P), n.data(), stride.data(), ns.data(), hs.data(),
-                                                   static_cast<int>(nb), g.data(), comp, win.data()))
+  std::size_t tot_smp = 0;
+  for (auto v : z.ns) tot_smp += v;
+  std::vector<T> hs(tot_smp);
+  gather_samples(z, smp, hs.data());
+  const std::vector<std::uint64_t> g = boundary_ranks(n);
+  std::vector<std::uint64_t> win(2 * P * nb), split(P * (nb + 1));
+  if (const char *why = dr_plan::split_windows_cmp(static_cast<int>(P), n.data(), z.stride.data(), z.ns.data(),
+                                                   hs.data(), static_cast<int>(nb), g.data(), comp, win.data()))
     throw std::runtime_error(std::string("shp::sort: ") + why);
-  std::size_t tot_win = 0;
-  for (std::size_t i = 0; i < P * nb; i++) tot_win += win[2 * i + 1] - win[2 * i];
-  std::vector<T> hw(tot_win);
-  for (std::size_t s = 0, off = 0; s < P; s++)
-    for (std::size_t k = 0; k < nb; k++) {
-      const std::size_t a = win[2 * (s * nb + k)], b = win[2 * (s * nb + k) + 1];
-      if (b > a)
-        check(drhip_memcpy_d2h(static_cast<int>(parts[s].rank()), hw.data() + off, parts[s].data() + a,
-                               (b - a) * sizeof(T)),
-              "sort slices d2h");
-      off += b - a;
-    }
-  for (std::size_t s = 0; s < P; s++) sync(parts[s].rank());
+  std::vector<T> hw(window_total(win));
+  gather_windows(z, win, hw.data());
   if (const char *why = dr_plan::split_exact_cmp(static_cast<int>(P), n.data(), static_cast<int>(nb), g.data(),
                                                  win.data(), hw.data(), comp, split.data()))
     throw std::runtime_error(std::string("shp::sort: ") + why);
-  auto sp = [&](std::size_t s, std::size_t k) -> std::size_t { return split[s * (nb + 1) + k]; };
   // 3. pieces into every destination's buffer, in source order
-  std::vector<std::vector<std::size_t>> offs(P, std::vector<std::size_t>(P + 1, 0));
-  for (std::size_t k = 0; k < P; k++) {
-    T *buf = reinterpret_cast<T *>(base[k]);
-    for (std::size_t s = 0; s < P; s++) {
-      const std::size_t a = k == 0 ? 0 : sp(s, k - 1), b = sp(s, k);
-      if (b > a)
-        check(drhip_memcpy_d2d(static_cast<int>(parts[k].rank()), buf + offs[k][s], parts[s].data() + a,
-                               (b - a) * sizeof(T)),
-              "sort piece copy");
-      offs[k][s + 1] = offs[k][s] + (b - a);
-    }
-    if (offs[k][P] != n[k]) throw std::runtime_error("shp::sort: splitting did not balance");
-  }
-  sync_all();
+  const auto offs = move_pieces("shp::sort", z.rank, n, split, {make_lane(z.parts, buf, "sort piece copy")});
   // 4. pairwise run merges, the last round into the segment: with R rounds
   //    and two buffers, the runs start in the segment when R is even
   std::size_t R = 0;
   while ((std::size_t(1) << R) < P) R++;
   for (std::size_t k = 0; k < P; k++) {
     hipStream_t s = st(k);
-    T *buf = reinterpret_cast<T *>(base[k]), *seg = parts[k].data();
-    T *src = buf, *dst = seg;
+    T *src = buf[k], *dst = z[k].data();
     if (R % 2 == 0) {
-      hip_check(hipMemcpyAsync(seg, buf, n[k] * sizeof(T), hipMemcpyDeviceToDevice, s), "sort run copy");
+      hip_check(hipMemcpyAsync(dst, src, n[k] * sizeof(T), hipMemcpyDeviceToDevice, s), "sort run copy");
       std::swap(src, dst);
     }
     // the tile splits: where the local sort kept its own, past the piece buffer
@@ -567,85 +536,57 @@ void sort_by_key(ExecutionPolicy &&policy, KR &&keys, VR &&values, Compare comp 
   constexpr std::size_t vb = sizeof(V);
   if (static_cast<std::size_t>(std::ranges::size(keys)) != static_cast<std::size_t>(std::ranges::size(values)))
     throw std::invalid_argument("shp::sort_by_key: keys and values differ in size");
-  std::vector<device_span<T>> parts;
+  const auto z = detail::nonempty_parts<T>(lib::ranges::segments(keys));
   std::vector<device_span<V>> vparts;
-  for (auto &&s : lib::ranges::segments(keys))
-    if (s.size()) parts.push_back(s);
   for (auto &&s : lib::ranges::segments(values))
     if (s.size()) vparts.push_back(s);
-  const std::size_t P = parts.size();
-  if (vparts.size() != P) throw std::invalid_argument("shp::sort_by_key: keys and values are segmented differently");
-  for (std::size_t k = 0; k < P; k++)
-    if (parts[k].size() != vparts[k].size() || parts[k].rank() != vparts[k].rank())
-      throw std::invalid_argument("shp::sort_by_key: keys and values are segmented differently");
+  detail::check_segmented_alike("shp::sort_by_key", z.parts, vparts);
+  const std::size_t P = z.size();
   if (P == 0) return;
-  std::vector<std::uint64_t> n(P), stride(P), ns(P);
+  const int dt = detail::dtype_code<T>();
+  std::vector<std::size_t> wsb(P), mwsb(P, 0);
+  std::vector<detail::sort_layout> lay(P);
   for (std::size_t k = 0; k < P; k++) {
-    n[k] = parts[k].size();
-    stride[k] = std::max<std::uint64_t>(1, (n[k] + detail::kSortSamples - 1) / detail::kSortSamples);
-    ns[k] = (n[k] + stride[k] - 1) / stride[k];
+    const int rk = static_cast<int>(z.rank[k]);
+    detail::check(drhip_sort_pairs_workspace(rk, dt, vb, z.n[k], &wsb[k]), "drhip_sort_pairs_workspace");
+    if (P > 1)
+      detail::check(drhip_merge_pairs_workspace(rk, dt, vb, z.n[k], static_cast<int>(P), &mwsb[k]),
+                    "drhip_merge_pairs_workspace");
+    lay[k] = detail::radix_sort_layout<T>(wsb[k], mwsb[k], z.n[k], vb, z.ns[k], P);
   }
-  std::vector<detail::sort_scratch> sc(P);
-  {
-    std::map<std::size_t, std::size_t> rank_bytes; // one scratch block per rank, carved per segment
-    for (std::size_t k = 0; k < P; k++) {
-      sc[k] = detail::size_pairs_scratch<T>(parts[k].rank(), n[k], P, ns[k], vb);
-      rank_bytes[parts[k].rank()] += sc[k].bytes;
-    }
-    std::map<std::size_t, char *> rank_next;
-    for (auto &[rk, b] : rank_bytes) rank_next[rk] = static_cast<char *>(detail::device_scratch().get(rk, b));
-    for (std::size_t k = 0; k < P; k++) {
-      char *&next = rank_next[parts[k].rank()];
-      detail::carve_pairs_scratch<T>(sc[k], next, n[k], P, vb);
-      next += sc[k].bytes;
-    }
+  const std::vector<char *> base = detail::carve_scratch(z.rank, lay);
+  std::vector<T *> buf(P), smp(P);
+  std::vector<V *> vbuf(P);
+  for (std::size_t k = 0; k < P; k++) {
+    buf[k] = lay[k].template at<T>(base[k], detail::SORT_BUF);
+    vbuf[k] = lay[k].template at<V>(base[k], detail::SORT_VBUF);
+    smp[k] = lay[k].template at<T>(base[k], detail::SORT_SMP);
   }
   // 1. local stable sorts of the pairs, then the regular key samples
   for (std::size_t k = 0; k < P; k++) {
-    const int rk = static_cast<int>(parts[k].rank());
-    if (n[k] > 1)
-      detail::check(drhip_sort_pairs(rk, detail::dtype_code<T>(), parts[k].data(), vparts[k].data(), vb, n[k], sc[k].ws,
-                                     sc[k].wsb),
+    const int rk = static_cast<int>(z.rank[k]);
+    if (z.n[k] > 1)
+      detail::check(drhip_sort_pairs(rk, dt, z[k].data(), vparts[k].data(), vb, z.n[k],
+                                     lay[k].at(base[k], detail::SORT_WS), wsb[k]),
                     "drhip_sort_pairs");
-    if (P > 1)
-      detail::check(drhip_sort_sample(rk, detail::dtype_code<T>(), parts[k].data(), n[k], stride[k], sc[k].smp),
-                    "drhip_sort_sample");
+    if (P > 1) detail::check(drhip_sort_sample(rk, dt, z[k].data(), z.n[k], z.stride[k], smp[k]), "drhip_sort_sample");
   }
   if (P == 1) {
-    sync(parts[0].rank());
+    sync(z.rank[0]);
     return;
   }
   // 2. exact splitting on the keys alone
-  const std::size_t nb = P - 1;
-  const std::vector<std::uint64_t> split = detail::exact_splits<T>(parts, sc, n, stride, ns);
-  auto sp = [&](std::size_t s, std::size_t k) -> std::size_t { return split[s * (nb + 1) + k]; };
+  const std::vector<std::uint64_t> split = detail::exact_splits<T>(z, smp);
   // 3. pieces, keys and values by the same indices, in source order
-  for (std::size_t k = 0; k < P; k++) {
-    std::size_t off = 0;
-    const int rk = static_cast<int>(parts[k].rank());
-    for (std::size_t s = 0; s < P; s++) {
-      const std::size_t a = k == 0 ? 0 : sp(s, k - 1), b = sp(s, k);
-      if (b > a) {
-        detail::check(drhip_memcpy_d2d(rk, static_cast<T *>(sc[k].buf) + off, parts[s].data() + a, (b - a) * sizeof(T)),
-                      "sort_by_key key piece copy");
-        detail::check(drhip_memcpy_d2d(rk, static_cast<V *>(sc[k].vbuf) + off, vparts[s].data() + a, (b - a) * vb),
-                      "sort_by_key value piece copy");
-      }
-      off += b - a;
-    }
-    if (off != n[k]) throw std::runtime_error("shp::sort_by_key: splitting did not balance");
-  }
-  sync_all();
+  const auto offs = detail::move_pieces("shp::sort_by_key", z.rank, z.n, split,
+                                        {detail::make_lane(z.parts, buf, "sort_by_key key piece copy"),
+                                         detail::make_lane(vparts, vbuf, "sort_by_key value piece copy")});
   // 4. stable merge of the P runs straight into the key and value segments
-  for (std::size_t k = 0; k < P; k++) {
-    const int rk = static_cast<int>(parts[k].rank());
-    std::vector<std::size_t> offs(P + 1, 0);
-    for (std::size_t s = 0; s < P; s++) offs[s + 1] = offs[s] + (sp(s, k) - (k == 0 ? 0 : sp(s, k - 1)));
-    detail::check(drhip_merge_pairs_runs_to(rk, detail::dtype_code<T>(), vb, sc[k].buf, sc[k].vbuf, parts[k].data(),
-                                            vparts[k].data(), n[k], offs.data(), static_cast<int>(P), sc[k].mws,
-                                            sc[k].mwsb),
+  for (std::size_t k = 0; k < P; k++)
+    detail::check(drhip_merge_pairs_runs_to(static_cast<int>(z.rank[k]), dt, vb, buf[k], vbuf[k], z[k].data(),
+                                            vparts[k].data(), z.n[k], offs[k].data(), static_cast<int>(P),
+                                            lay[k].at(base[k], detail::SORT_MWS), mwsb[k]),
                   "drhip_merge_pairs_runs_to");
-  }
   sync_all();
   }
 }

@@ -267,6 +267,30 @@ TEST(ScratchReusedAndRegrown) {
   whole_case<int>(1000, 102, pred);
 }
 
+// every input segment cut at a third, both parts listed: two pieces share
+// every rank's scratch block, each with its own compacted piece and status
+TEST(SharedRankSegments) {
+  const std::size_t n = (std::size_t(1) << 21) + 13;
+  const std::vector<int> h = make_data<int>(n, 110);
+  auto pred = [] __host__ __device__(int x) { return (x & 3) != 0; };
+  shp::distributed_vector<int> in(n), out(n, -7);
+  shp::copy(h.begin(), h.end(), in.begin());
+  std::vector<shp::device_span<int>> parts;
+  for (auto &&s : in.segments()) {
+    const std::size_t a = s.size() / 3;
+    parts.emplace_back(s.data(), a, s.rank());
+    parts.emplace_back(s.data() + a, s.size() - a, s.rank());
+  }
+  shp::distributed_span<int> ds(parts);
+  std::vector<int> want;
+  std::copy_if(h.begin(), h.end(), std::back_inserter(want), pred);
+  EXPECT_TRUE(shp::count_if(shp::par_unseq, ds, pred) == want.size());
+  auto it = shp::copy_if(shp::par_unseq, ds, out, pred);
+  EXPECT_TRUE(it == out.begin() + (std::ptrdiff_t)want.size());
+  want.resize(n, -7);
+  EXPECT_TRUE(to_host(out) == want);
+}
+
 int main(int argc, char **argv) {
   unsigned dev_num = 0;
   std::string filter, dev_list;

@@ -419,6 +419,58 @@ TEST(IteratorForms) {
   EXPECT_TRUE(to_host(uk) == ek);
 }
 
+// every segment cut at a third, both parts listed: two pieces per rank
+template <typename T> static shp::distributed_span<T> cut_in_two(shp::distributed_vector<T> &dv) {
+  std::vector<shp::device_span<T>> parts;
+  for (auto &&s : dv.segments()) {
+    const std::size_t a = s.size() / 3;
+    parts.emplace_back(s.data(), a, s.rank());
+    parts.emplace_back(s.data() + a, s.size() - a, s.rank());
+  }
+  return shp::distributed_span<T>(parts);
+}
+
+// two pieces share every rank's scratch block, each with its own runs and
+// state; runs cross the cuts as they cross segment boundaries
+TEST(SharedRankSegments) {
+  const std::size_t n = (std::size_t(1) << 20) + 13;
+  for (double mean : {3.0, 1000.0}) {
+    const std::vector<int> k = run_keys(n, mean, 27);
+    const std::vector<int> v = small_values<int>(n, 28);
+    std::vector<int> wk, wv, tmp;
+    std::vector<std::uint64_t> ones(n, 1), wc;
+    host_rbk(k, v, wk, wv, std::equal_to<>{}, std::plus<>{});
+    host_rbk(k, ones, tmp, wc, std::equal_to<>{}, std::plus<>{});
+    const std::ptrdiff_t runs = (std::ptrdiff_t)wk.size();
+    wk.resize(n, -7);
+    wv.resize(n, -7);
+    wc.resize(n, 0);
+    auto dk = to_device(k);
+    auto dv = to_device(v);
+    auto ks = cut_in_two(dk);
+    auto vs = cut_in_two(dv);
+    {
+      shp::distributed_vector<int> ok(n, -7), ov(n, -7);
+      auto [ik, iv] = shp::reduce_by_key(shp::par_unseq, ks, vs, ok, ov);
+      EXPECT_TRUE(ik == ok.begin() + runs && iv == ov.begin() + runs);
+      EXPECT_TRUE(to_host(ok) == wk && to_host(ov) == wv);
+    }
+    {
+      shp::distributed_vector<int> ok(n, -7);
+      shp::distributed_vector<std::uint64_t> oc(n, 0);
+      auto [ik, ic] = shp::run_length_encode(shp::par_unseq, ks, ok, oc);
+      EXPECT_TRUE(ik == ok.begin() + runs && ic == oc.begin() + runs);
+      EXPECT_TRUE(to_host(ok) == wk && to_host(oc) == wc);
+    }
+    {
+      shp::distributed_vector<int> ok(n, -7);
+      auto it = shp::unique_copy(shp::par_unseq, ks, ok);
+      EXPECT_TRUE(it == ok.begin() + runs);
+      EXPECT_TRUE(to_host(ok) == wk);
+    }
+  }
+}
+
 int main(int argc, char **argv) {
   unsigned dev_num = 0;
   std::string filter, dev_list;

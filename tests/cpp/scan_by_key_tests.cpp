@@ -337,6 +337,62 @@ TEST(IteratorForms) {
   EXPECT_TRUE(to_host(o2) == ee);
 }
 
+// every segment cut at a third, both parts listed: two pieces per rank
+template <typename T> static shp::distributed_span<T> cut_in_two(shp::distributed_vector<T> &dv) {
+  std::vector<shp::device_span<T>> parts;
+  for (auto &&s : dv.segments()) {
+    const std::size_t a = s.size() / 3;
+    parts.emplace_back(s.data(), a, s.rank());
+    parts.emplace_back(s.data() + a, s.size() - a, s.rank());
+  }
+  return shp::distributed_span<T>(parts);
+}
+
+// two pieces share every rank's scratch block: written directly (state only),
+// through scratch (an output out of step with the input) and in place (the
+// exclusive form keeps a copy of a piece's values there)
+TEST(SharedRankSegments) {
+  const std::size_t n = (std::size_t(1) << 20) + 13;
+  for (double mean : {3.0, 1000.0}) {
+    const std::vector<int> k = run_keys(n, mean, 25);
+    const std::vector<int> v = small_values<int>(n, 26);
+    const auto wi = host_incl(k, v, std::equal_to<>{}, std::plus<>{});
+    const auto we = host_excl(k, v, 5, std::equal_to<>{}, std::plus<>{});
+    auto dk = to_device(k);
+    auto dv = to_device(v);
+    auto ks = cut_in_two(dk);
+    auto vs = cut_in_two(dv);
+    {
+      shp::distributed_vector<int> o(n, -7);
+      shp::inclusive_scan_by_key(shp::par_unseq, ks, vs, o);
+      EXPECT_TRUE(to_host(o) == wi);
+      shp::exclusive_scan_by_key(shp::par_unseq, ks, vs, o, 5);
+      EXPECT_TRUE(to_host(o) == we);
+    }
+    {
+      const std::size_t drop = n / 3 + 1;
+      std::vector<int> ei(n + drop, -7), ee(n + drop, -7);
+      std::copy(wi.begin(), wi.end(), ei.begin() + (std::ptrdiff_t)drop);
+      std::copy(we.begin(), we.end(), ee.begin() + (std::ptrdiff_t)drop);
+      shp::distributed_vector<int> o(n + drop, -7), o2(n + drop, -7);
+      shp::inclusive_scan_by_key(shp::par_unseq, ks, vs, o | shp::views::drop(drop));
+      EXPECT_TRUE(to_host(o) == ei);
+      shp::exclusive_scan_by_key(shp::par_unseq, ks, vs, o2 | shp::views::drop(drop), 5);
+      EXPECT_TRUE(to_host(o2) == ee);
+    }
+    {
+      auto d1 = to_device(v);
+      auto s1 = cut_in_two(d1);
+      shp::inclusive_scan_by_key(shp::par_unseq, ks, s1, s1);
+      EXPECT_TRUE(to_host(d1) == wi);
+      auto d2 = to_device(v);
+      auto s2 = cut_in_two(d2);
+      shp::exclusive_scan_by_key(shp::par_unseq, ks, s2, s2, 5);
+      EXPECT_TRUE(to_host(d2) == we);
+    }
+  }
+}
+
 int main(int argc, char **argv) {
   unsigned dev_num = 0;
   std::string filter, dev_list;

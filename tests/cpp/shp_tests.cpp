@@ -480,9 +480,9 @@ TEST(ShpExtra, SortSplitShapes) {
 
 TEST(ShpExtra, SortSharedRankSegments) {
   // a distributed_span listing two segments of the SAME rank (every rank's
-  // segment cut in two): shp::sort carves one scratch block per rank into
-  // disjoint per-segment slices (sort.hpp) -- each piece's exchange buffer
-  // must survive until its merge
+  // segment cut in two): one scratch block per rank is carved into disjoint
+  // per-segment slices (detail::carve_scratch, runtime.hpp) -- each piece's
+  // exchange buffer must survive until its merge
   const std::size_t n = 4 * (std::size_t(1) << 16) + 321;
   std::vector<std::uint32_t> h(n);
   std::mt19937_64 g(21);
@@ -602,6 +602,25 @@ TEST(ShpExtra, SortGeneralComparator) {
     auto by_mod = [](std::uint32_t a, std::uint32_t b) { return a % 1000 < b % 1000; };
     shp::stable_sort(shp::par_unseq, dv.begin() + 17, dv.end() - 1001, by_mod);
     std::stable_sort(h.begin() + 17, h.end() - 1001, by_mod);
+    EXPECT_TRUE(same_bytes_v(to_host(dv), h));
+  }
+  // two segments of every rank (SortSharedRankSegments' shape): each piece's
+  // local-sort scratch doubles as its exchange buffer until its merge
+  {
+    const std::size_t n = 4 * (std::size_t(1) << 16) + 321;
+    std::vector<rec16> h(n);
+    for (std::size_t i = 0; i < n; i++) h[i] = {static_cast<std::uint32_t>(g() % 97), static_cast<std::uint32_t>(i), 7u, 9u};
+    shp::distributed_vector<rec16> dv(n);
+    shp::copy(h.begin(), h.end(), dv.begin());
+    std::vector<shp::device_span<rec16>> parts;
+    for (auto &&s : dv.segments()) {
+      const std::size_t a = s.size() / 3;
+      parts.emplace_back(s.data(), a, s.rank());
+      parts.emplace_back(s.data() + a, s.size() - a, s.rank());
+    }
+    auto by_key = [](const rec16 &a, const rec16 &b) { return a.key < b.key; };
+    shp::sort(shp::par_unseq, shp::distributed_span(parts), by_key);
+    std::stable_sort(h.begin(), h.end(), by_key);
     EXPECT_TRUE(same_bytes_v(to_host(dv), h));
   }
 }

@@ -170,6 +170,33 @@ TEST(ScratchReusedAndRegrown) {
   pairs_case<std::uint32_t, std::uint32_t>(1000, 53, 0);
 }
 
+// every segment cut at a third, both parts listed: two pieces per rank
+template <typename T> static shp::distributed_span<T> cut_in_two(shp::distributed_vector<T> &dv) {
+  std::vector<shp::device_span<T>> parts;
+  for (auto &&s : dv.segments()) {
+    const std::size_t a = s.size() / 3;
+    parts.emplace_back(s.data(), a, s.rank());
+    parts.emplace_back(s.data() + a, s.size() - a, s.rank());
+  }
+  return shp::distributed_span<T>(parts);
+}
+
+// two pieces share every rank's scratch block: both exchange buffers of each
+// must survive until its merge.  Few distinct keys, the value is the original
+// index: ties across the pieces of one rank show in the values.
+TEST(SharedRankSegments) {
+  const std::size_t n = 4 * (std::size_t(1) << 16) + 321;
+  std::vector<std::uint32_t> hk = make_keys<std::uint32_t>(n, 60, 1000), hv(n);
+  for (std::size_t i = 0; i < n; i++) hv[i] = (std::uint32_t)i;
+  shp::distributed_vector<std::uint32_t> dk(n), dv(n);
+  shp::copy(hk.begin(), hk.end(), dk.begin());
+  shp::copy(hv.begin(), hv.end(), dv.begin());
+  shp::sort_by_key(shp::par_unseq, cut_in_two(dk), cut_in_two(dv));
+  host_sort(hk, hv, 0, n, std::less<>());
+  EXPECT_TRUE(same_bits(to_host(dk), hk));
+  EXPECT_TRUE(same_bits(to_host(dv), hv));
+}
+
 TEST(MismatchesThrow) {
   shp::distributed_vector<std::uint32_t> dk(1000), dv(1000), ds(999);
   shp::fill(dk.begin(), dk.end(), 3u);

@@ -10,7 +10,11 @@
 //   * the bracket [lo_k, hi_k] holds the key of global rank g_k;
 //   * every rank's window [a, b) holds every key of the bracket;
 //   * split sizes sum to min(g_k, N) and grow with k on every rank;
-//   * exact partition: every key below a split <= every key above it.
+//   * exact partition: every key below a split <= every key above it;
+//   * the run plan of every destination (plan_runs): offsets from 0 to the
+//     destination's size, never decreasing, and over all destinations every
+//     source key exactly once.
+// And the sample plan (plan_samples) at the sizes around its 65536-sample limit.
 #include <dr/details/split_plan.hpp>
 
 #include <algorithm>
@@ -29,6 +33,22 @@ static int g_fail = 0;
     }                                                                            \
   } while (0)
 static int g_case = 0;
+
+// the run plans of a split table with nd columns whose destination k must receive want[k] keys
+static void check_run_plans(const std::vector<u64> &split, int p, int nd, const std::vector<u64> &n, const std::vector<u64> &want) {
+  std::vector<u64> next(p, 0); // the source keys handed out so far: destination k's range must start here
+  for (int k = 0; k < nd; k++) {
+    const dr_plan::run_plan r = dr_plan::plan_runs(split.data(), p, nd, k);
+    CHECK(r.from.size() == (std::size_t)p && r.offs.size() == (std::size_t)p + 1);
+    CHECK(r.offs[0] == 0 && r.offs[p] == want[k]);
+    for (int s = 0; s < p; s++) {
+      CHECK(r.offs[s + 1] >= r.offs[s]);
+      CHECK(r.from[s] == next[s]);
+      next[s] += r.offs[s + 1] - r.offs[s];
+    }
+  }
+  for (int s = 0; s < p; s++) CHECK(next[s] == n[s]);
+}
 
 static void one_case(std::mt19937_64 &rng) {
   const int p = 1 + (int)(rng() % 9);
@@ -94,6 +114,9 @@ static void one_case(std::mt19937_64 &rng) {
     if (any_below && above_min != ~u64(0)) CHECK(below_max <= above_min);
   }
   for (int i = 0; i < p; i++) CHECK(split[(std::size_t)i * (nb + 1) + nb] == n[i]);
+  std::vector<u64> want(nb + 1); // destination k holds the global ranks [g_{k-1}, g_k), the last the rest
+  for (int k = 0; k <= nb; k++) want[k] = (k < nb ? std::min(g[k], ntot) : ntot) - (k ? std::min(g[k - 1], ntot) : 0);
+  check_run_plans(split, p, nb + 1, n, want);
 }
 
 // The comparator form (split_windows_cmp / split_exact_cmp, shp::sort's
@@ -151,10 +174,12 @@ static void one_cmp_case(std::mt19937_64 &rng) {
   std::vector<rec> out;
   for (int k = 0; k < p; k++) {
     std::vector<rec> d;
+    const dr_plan::run_plan r = dr_plan::plan_runs(split.data(), p, p, k);
     for (int i = 0; i < p; i++) {
-      const u64 a = k ? split[(std::size_t)i * (nb + 1) + k - 1] : 0, b = split[(std::size_t)i * (nb + 1) + k];
-      CHECK(a <= b);
-      if (a > b) return;
+      const u64 a = r.from[i], b = split[(std::size_t)i * (nb + 1) + k];
+      CHECK(a <= b && b <= n[i]);
+      if (a > b || b > n[i]) return;
+      CHECK(r.offs[i] == d.size() && r.offs[i + 1] == d.size() + (b - a)); // run i lands behind the runs before it
       d.insert(d.end(), keys[i].begin() + a, keys[i].begin() + b);
     }
     if (k + 1 < p) CHECK(d.size() == (k ? g[k] - g[k - 1] : g[0]));
@@ -174,6 +199,18 @@ int main(int argc, char **argv) {
   std::mt19937_64 rng(0x5eed);
   for (g_case = 0; g_case < cases; g_case++) one_case(rng);
   for (g_case = 0; g_case < cases; g_case++) one_cmp_case(rng);
+  // the sample plan: stride 1 up to the limit, then the smallest stride that keeps ns within it
+  const u64 sizes[] = {0, 1, 65535, 65536, 65537, (u64(1) << 32) + 5};
+  const u64 want[][2] = {{1, 0}, {1, 1}, {1, 65535}, {1, 65536}, {2, 32769}, {65537, 65536}};
+  for (int i = 0; i < 6; i++) {
+    const u64 n = sizes[i];
+    const dr_plan::sample_plan sp = dr_plan::plan_samples(n);
+    CHECK(sp.stride >= 1);
+    CHECK(sp.ns == (n + sp.stride - 1) / sp.stride);
+    CHECK(sp.ns <= 65536);
+    if (n) CHECK((sp.ns - 1) * sp.stride < n);
+    CHECK(sp.stride == want[i][0] && sp.ns == want[i][1]);
+  }
   // refused arguments
   u64 one = 1;
   CHECK(dr_plan::split_windows(0, &one, &one, &one, &one, 0, nullptr, nullptr, nullptr, nullptr) != nullptr);
