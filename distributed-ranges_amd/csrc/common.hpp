@@ -207,6 +207,18 @@ template <typename F> int dispatch_op(int op, F &&f) {
   }
 }
 
+template <typename F> int dispatch_cmp(int cmp, const char *fn, F &&f) {
+  switch (cmp) {
+  case DRHIP_LT: return f(std::integral_constant<int, DRHIP_LT>{});
+  case DRHIP_LE: return f(std::integral_constant<int, DRHIP_LE>{});
+  case DRHIP_GT: return f(std::integral_constant<int, DRHIP_GT>{});
+  case DRHIP_GE: return f(std::integral_constant<int, DRHIP_GE>{});
+  case DRHIP_EQ: return f(std::integral_constant<int, DRHIP_EQ>{});
+  case DRHIP_NE: return f(std::integral_constant<int, DRHIP_NE>{});
+  default: return set_error(DRHIP_ERR_BAD_ARG, fn);
+  }
+}
+
 template <typename T> constexpr int dtype_code_of() {
   if constexpr (std::is_same_v<T, int32_t>) return DRHIP_I32;
   else if constexpr (std::is_same_v<T, uint32_t>) return DRHIP_U32;
@@ -400,6 +412,18 @@ template <typename T> __device__ __forceinline__ T from_bits64(uint64_t u) {
   return r;
 }
 
+// in[i] CMP scalar with the C++ operators of T (IEEE for floats)
+template <typename T, int CMP> struct CmpPred {
+  T s;
+  __device__ __forceinline__ bool operator()(const T &v, size_t) const {
+    if constexpr (CMP == DRHIP_LT) return v < s;
+    else if constexpr (CMP == DRHIP_LE) return v <= s;
+    else if constexpr (CMP == DRHIP_GT) return v > s;
+    else if constexpr (CMP == DRHIP_GE) return v >= s;
+    else if constexpr (CMP == DRHIP_EQ) return v == s;
+    else return v != s;
+  }
+};
 inline unsigned grid_cap(const Segment *s, int blocks_per_cu) {
   return (unsigned)(s->num_cus * blocks_per_cu);
 }

@@ -9,35 +9,11 @@ namespace drhip {
 
 using namespace dr_select;
 
-// in[i] CMP scalar with the C++ operators of T (IEEE for floats)
-template <typename T, int CMP> struct CmpPred {
-  T s;
-  __device__ __forceinline__ bool operator()(const T &v, size_t) const {
-    if constexpr (CMP == DRHIP_LT) return v < s;
-    else if constexpr (CMP == DRHIP_LE) return v <= s;
-    else if constexpr (CMP == DRHIP_GT) return v > s;
-    else if constexpr (CMP == DRHIP_GE) return v >= s;
-    else if constexpr (CMP == DRHIP_EQ) return v == s;
-    else return v != s;
-  }
-};
 struct FlagPred {
   const uint8_t *f;
   __device__ __forceinline__ bool operator()(const uint32_t &, size_t i) const { return f[i] != 0; }
   __device__ __forceinline__ bool operator()(const uint64_t &, size_t i) const { return f[i] != 0; }
 };
-
-template <typename F> static int dispatch_cmp(int cmp, const char *fn, F &&f) {
-  switch (cmp) {
-  case DRHIP_LT: return f(std::integral_constant<int, DRHIP_LT>{});
-  case DRHIP_LE: return f(std::integral_constant<int, DRHIP_LE>{});
-  case DRHIP_GT: return f(std::integral_constant<int, DRHIP_GT>{});
-  case DRHIP_GE: return f(std::integral_constant<int, DRHIP_GE>{});
-  case DRHIP_EQ: return f(std::integral_constant<int, DRHIP_EQ>{});
-  case DRHIP_NE: return f(std::integral_constant<int, DRHIP_NE>{});
-  default: return set_error(DRHIP_ERR_BAD_ARG, fn);
-  }
-}
 
 static bool overlaps(const void *a, size_t ab, const void *b, size_t bb) {
   const uintptr_t a0 = (uintptr_t)a, b0 = (uintptr_t)b;

@@ -60,6 +60,8 @@ EXPORTS = [
     "drhip_count_if", "drhip_copy_if", "drhip_copy_flagged",
     "drhip_reduce_by_key", "drhip_run_length_encode", "drhip_unique_copy",
     "drhip_inclusive_scan_by_key", "drhip_exclusive_scan_by_key",
+    "drhip_find_if", "drhip_is_sorted_until", "drhip_mismatch",
+    "drhip_min_element", "drhip_max_element", "drhip_minmax_element",
     "drhip_comm_unique_id", "drhip_comm_init_rank", "drhip_comm_init_all", "drhip_comm_destroy",
     "drhip_comm_rank", "drhip_comm_group_start", "drhip_comm_group_end", "drhip_allreduce",
     "drhip_allgather", "drhip_gather", "drhip_alltoallv", "drhip_halo_exchange",
@@ -127,6 +129,9 @@ def load():
         "drhip_run_length_encode": [i, i, vp, sz, vp, vp, vp], "drhip_unique_copy": [i, i, vp, sz, vp, vp],
         "drhip_inclusive_scan_by_key": [i, i, i, i, vp, vp, sz, vp],
         "drhip_exclusive_scan_by_key": [i, i, i, i, vp, vp, sz, vp, vp],
+        "drhip_find_if": [i, i, i, vp, sz, vp, vp], "drhip_is_sorted_until": [i, i, vp, sz, vp],
+        "drhip_mismatch": [i, i, vp, vp, sz, vp], "drhip_min_element": [i, i, vp, sz, vp],
+        "drhip_max_element": [i, i, vp, sz, vp], "drhip_minmax_element": [i, i, vp, sz, vp],
         "drhip_comm_unique_id": [vp], "drhip_comm_init_rank": [i, i, i, vp], "drhip_comm_init_all": [],
         "drhip_comm_destroy": [i], "drhip_comm_rank": [i, vp, vp], "drhip_comm_group_start": [],
         "drhip_comm_group_end": [], "drhip_allreduce": [i, i, i, vp, vp, sz], "drhip_allgather": [i, vp, vp, sz],
@@ -463,6 +468,37 @@ def copy_flagged_async(seg, elem_bytes, src, flags, dst, n, count_dev):
     check(load().drhip_copy_flagged(seg, elem_bytes, src, flags, dst, n, count_dev))
 
 
+def find_if_async(seg, dtype, cmp, x, n, scalar, index_dev):
+    """drhip_find_if: *index_dev (uint64, device-visible) = the least i with x[i] cmp scalar, or n."""
+    v = _scalar(scalar, dtype)
+    check(load().drhip_find_if(seg, DTYPES[np.dtype(dtype)], _cmp(cmp), x, n, _hp(v), index_dev))
+
+
+def is_sorted_until_async(seg, dtype, x, n, index_dev):
+    """drhip_is_sorted_until: *index_dev = the least i >= 1 with x[i] < x[i-1], or n."""
+    check(load().drhip_is_sorted_until(seg, DTYPES[np.dtype(dtype)], x, n, index_dev))
+
+
+def mismatch_async(seg, dtype, a, b, n, index_dev):
+    """drhip_mismatch: *index_dev = the least i with a[i] != b[i], or n."""
+    check(load().drhip_mismatch(seg, DTYPES[np.dtype(dtype)], a, b, n, index_dev))
+
+
+def min_element_async(seg, dtype, x, n, index_dev):
+    """drhip_min_element: *index_dev = the index of the first least element."""
+    check(load().drhip_min_element(seg, DTYPES[np.dtype(dtype)], x, n, index_dev))
+
+
+def max_element_async(seg, dtype, x, n, index_dev):
+    """drhip_max_element: *index_dev = the index of the first greatest element."""
+    check(load().drhip_max_element(seg, DTYPES[np.dtype(dtype)], x, n, index_dev))
+
+
+def minmax_element_async(seg, dtype, x, n, idx2_dev):
+    """drhip_minmax_element: idx2_dev[0] = the first least, idx2_dev[1] = the LAST greatest element's index."""
+    check(load().drhip_minmax_element(seg, DTYPES[np.dtype(dtype)], x, n, idx2_dev))
+
+
 def _op(op):
     return OPS[op] if isinstance(op, str) else int(op)
 
@@ -671,6 +707,42 @@ def run_length_encode(seg, keys_ptr, n, kdtype, keys_out_ptr, counts_out_ptr):
 def unique_copy(seg, keys_ptr, n, kdtype, keys_out_ptr):
     """Every run's first key (blocking); returns the number of runs."""
     return _with_count(seg, lambda c: unique_copy_async(seg, kdtype, keys_ptr, n, keys_out_ptr, c))
+
+
+def find_if(seg, x_ptr, n, dtype, cmp, scalar):
+    """The least i with x[i] cmp scalar among the n elements at device address x_ptr, or n (blocking)."""
+    return _with_count(seg, lambda c: find_if_async(seg, dtype, cmp, x_ptr, n, scalar, c))
+
+
+def is_sorted_until(seg, x_ptr, n, dtype):
+    """The length of the longest sorted prefix: the least i >= 1 with x[i] < x[i-1], or n (blocking)."""
+    return _with_count(seg, lambda c: is_sorted_until_async(seg, dtype, x_ptr, n, c))
+
+
+def mismatch(seg, a_ptr, b_ptr, n, dtype):
+    """The least i with a[i] != b[i], or n (blocking)."""
+    return _with_count(seg, lambda c: mismatch_async(seg, dtype, a_ptr, b_ptr, n, c))
+
+
+def min_element(seg, x_ptr, n, dtype):
+    """The index of the first least element; 0 when n == 0 (blocking)."""
+    return _with_count(seg, lambda c: min_element_async(seg, dtype, x_ptr, n, c))
+
+
+def max_element(seg, x_ptr, n, dtype):
+    """The index of the first greatest element; 0 when n == 0 (blocking)."""
+    return _with_count(seg, lambda c: max_element_async(seg, dtype, x_ptr, n, c))
+
+
+def minmax_element(seg, x_ptr, n, dtype):
+    """(index of the first least, index of the LAST greatest element), one read of x (blocking)."""
+    out = DeviceArray(seg, 2, np.uint64)
+    try:
+        minmax_element_async(seg, dtype, x_ptr, n, out.ptr)
+        r = out.numpy()
+        return int(r[0]), int(r[1])
+    finally:
+        out.free()
 
 
 def inclusive_scan_by_key(seg, keys_ptr, vals_ptr, n, kdtype, vdtype, vals_out_ptr, op="plus"):

@@ -714,6 +714,14 @@ public:
     iterator &operator++() { ++i; return *this; }
     iterator operator++(int) { auto x = *this; ++i; return x; }
     bool operator==(const iterator &o) const { return i == o.i; }
+    // a position found by an algorithm (dr/shp/search.hpp): begin() + k, and k back as it - begin()
+    friend iterator operator+(iterator a, difference_type d) {
+      a.i = static_cast<std::size_t>(static_cast<difference_type>(a.i) + d);
+      return a;
+    }
+    friend difference_type operator-(const iterator &a, const iterator &b) {
+      return static_cast<difference_type>(a.i) - static_cast<difference_type>(b.i);
+    }
   };
   iterator begin() const { return {this, 0}; }
   iterator end() const { return {this, size()}; }

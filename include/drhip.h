@@ -474,6 +474,46 @@ int drhip_inclusive_scan_by_key(int seg, int kdtype, int vdtype, int op, const v
 int drhip_exclusive_scan_by_key(int seg, int kdtype, int vdtype, int op, const void *keys_in, const void *vals_in, size_t n,
                                 const void *init_host, void *vals_out);
 
+/* ----------------------------------------------------------- search ----
+ * The algorithms that answer a question about a range with a position:
+ * std::find_if, std::is_sorted_until, std::mismatch, std::min_element,
+ * std::max_element, std::minmax_element.  Absent from the reference; what
+ * they replace is a copy of the segment to the host and a host loop.
+ * Kernels: include/dr/details/search_kernel.hpp.
+ * First match (find_if, is_sorted_until, mismatch): the answer is the least
+ * matching index, exactly, whatever order the workgroups run in; a workgroup
+ * stops reading once a match below its next tile is recorded, so a match at
+ * position p costs about p / n of a full pass.  drhip_find_if's predicate is
+ * `x[i] cmp *scalar_host` as in drhip_count_if (IEEE for floats: a NaN passes
+ * only DRHIP_NE, -0.0 == +0.0); scalar_host (element type) is read during the
+ * call.
+ * Extrema compare with the C++ < of the element type; among equal elements
+ * the FIRST wins, except the maximum of drhip_minmax_element, where the LAST
+ * wins (std::minmax_element).  -0.0 and +0.0 are equal.  A NaN in an extremum
+ * or sortedness input gives an unspecified index.
+ * Asynchronous on the segment's stream.  index / idx2 (uint64, device-visible:
+ * device or pinned host memory, not null) are written by a kernel in stream
+ * order; with n == 0 they still receive 0 and nothing else is touched.
+ * DRHIP_ERR_BAD_ARG: an unknown dtype or cmp, a null pointer with n > 0, a
+ * null index and n >= 2^32 (positions are 32-bit inside the kernels); the
+ * arguments are checked before the segment, so a refusal leaves *index
+ * untouched.  The state (the result word; the workgroups' candidates) lives
+ * in the segment's workspace, which grows on demand -- not while a graph of
+ * the segment is alive or being captured (DRHIP_ERR_UNSUPPORTED: warm up with
+ * one eager call, as for drhip_copy_if); the result word is reset by a memset
+ * node before every launch, so a graph replay recomputes everything. */
+/* least i with x[i] cmp *scalar_host (drhip_cmp, IEEE rules as drhip_count_if); n if none */
+int drhip_find_if(int seg, int dtype, int cmp, const void *x, size_t n, const void *scalar_host, uint64_t *index);
+/* least i >= 1 with x[i] < x[i-1] (std::is_sorted_until under std::less); n if sorted or n < 2 */
+int drhip_is_sorted_until(int seg, int dtype, const void *x, size_t n, uint64_t *index);
+/* least i with a[i] != b[i]; n if none */
+int drhip_mismatch(int seg, int dtype, const void *a, const void *b, size_t n, uint64_t *index);
+/* first least / first greatest element under operator<; n (= 0) when n == 0 */
+int drhip_min_element(int seg, int dtype, const void *x, size_t n, uint64_t *index);
+int drhip_max_element(int seg, int dtype, const void *x, size_t n, uint64_t *index);
+/* idx2[0] = first least, idx2[1] = LAST greatest (std::minmax_element), one read of x */
+int drhip_minmax_element(int seg, int dtype, const void *x, size_t n, uint64_t *idx2);
+
 /* ---------------------------------------------------------- stencil ----
  * mhp::transform of a radius-r 1-D stencil over a halo'd segment
  * (mhp/algorithms/cpu_algorithms.hpp:147-161 with the ops of
