@@ -62,6 +62,7 @@ EXPORTS = [
     "drhip_inclusive_scan_by_key", "drhip_exclusive_scan_by_key",
     "drhip_find_if", "drhip_is_sorted_until", "drhip_mismatch",
     "drhip_min_element", "drhip_max_element", "drhip_minmax_element",
+    "drhip_lower_bound", "drhip_upper_bound", "drhip_binary_search",
     "drhip_comm_unique_id", "drhip_comm_init_rank", "drhip_comm_init_all", "drhip_comm_destroy",
     "drhip_comm_rank", "drhip_comm_group_start", "drhip_comm_group_end", "drhip_allreduce",
     "drhip_allgather", "drhip_gather", "drhip_alltoallv", "drhip_halo_exchange",
@@ -132,6 +133,8 @@ def load():
         "drhip_find_if": [i, i, i, vp, sz, vp, vp], "drhip_is_sorted_until": [i, i, vp, sz, vp],
         "drhip_mismatch": [i, i, vp, vp, sz, vp], "drhip_min_element": [i, i, vp, sz, vp],
         "drhip_max_element": [i, i, vp, sz, vp], "drhip_minmax_element": [i, i, vp, sz, vp],
+        "drhip_lower_bound": [i, i, vp, sz, vp, sz, vp], "drhip_upper_bound": [i, i, vp, sz, vp, sz, vp],
+        "drhip_binary_search": [i, i, vp, sz, vp, sz, vp],
         "drhip_comm_unique_id": [vp], "drhip_comm_init_rank": [i, i, i, vp], "drhip_comm_init_all": [],
         "drhip_comm_destroy": [i], "drhip_comm_rank": [i, vp, vp], "drhip_comm_group_start": [],
         "drhip_comm_group_end": [], "drhip_allreduce": [i, i, i, vp, vp, sz], "drhip_allgather": [i, vp, vp, sz],
@@ -499,6 +502,26 @@ def minmax_element_async(seg, dtype, x, n, idx2_dev):
     check(load().drhip_minmax_element(seg, DTYPES[np.dtype(dtype)], x, n, idx2_dev))
 
 
+# The haystack elements a workgroup of the sorted searches stages in LDS, by element bytes
+# (DRHIP_SORTED_SEARCH_STAGE of drhip.h); a call with fewer needles searches global memory directly.
+SORTED_SEARCH_STAGE = {4: 8192, 8: 8192}
+
+
+def lower_bound_async(seg, dtype, hay, n, needles, m, pos_dev):
+    """drhip_lower_bound: pos_dev[i] (uint64) = the least p in [0, n] with not hay[p] < needles[i]."""
+    check(load().drhip_lower_bound(seg, DTYPES[np.dtype(dtype)], hay, n, needles, m, pos_dev))
+
+
+def upper_bound_async(seg, dtype, hay, n, needles, m, pos_dev):
+    """drhip_upper_bound: pos_dev[i] (uint64) = the least p in [0, n] with needles[i] < hay[p]."""
+    check(load().drhip_upper_bound(seg, DTYPES[np.dtype(dtype)], hay, n, needles, m, pos_dev))
+
+
+def binary_search_async(seg, dtype, hay, n, needles, m, found_dev):
+    """drhip_binary_search: found_dev[i] (uint8) = 1 if needles[i] is in the sorted hay[0, n), else 0."""
+    check(load().drhip_binary_search(seg, DTYPES[np.dtype(dtype)], hay, n, needles, m, found_dev))
+
+
 def _op(op):
     return OPS[op] if isinstance(op, str) else int(op)
 
@@ -755,3 +778,27 @@ def exclusive_scan_by_key(seg, keys_ptr, vals_ptr, n, kdtype, vdtype, vals_out_p
     """The running fold of every run before each element, seeded with init (blocking)."""
     exclusive_scan_by_key_async(seg, kdtype, vdtype, op, keys_ptr, vals_ptr, n, vals_out_ptr, init)
     sync(seg)
+
+
+def _sorted_search(seg, call, m, out_dtype):
+    out = DeviceArray(seg, m, out_dtype)
+    try:
+        call(out.ptr)
+        return out.numpy()
+    finally:
+        out.free()
+
+
+def lower_bound(seg, hay_ptr, n, needles_ptr, m, dtype):
+    """numpy.searchsorted(hay, needles, 'left') of the sorted n elements at hay_ptr (blocking); uint64[m]."""
+    return _sorted_search(seg, lambda o: lower_bound_async(seg, dtype, hay_ptr, n, needles_ptr, m, o), m, np.uint64)
+
+
+def upper_bound(seg, hay_ptr, n, needles_ptr, m, dtype):
+    """numpy.searchsorted(hay, needles, 'right') of the sorted n elements at hay_ptr (blocking); uint64[m]."""
+    return _sorted_search(seg, lambda o: upper_bound_async(seg, dtype, hay_ptr, n, needles_ptr, m, o), m, np.uint64)
+
+
+def binary_search(seg, hay_ptr, n, needles_ptr, m, dtype):
+    """Whether each of the m needles is in the sorted n elements at hay_ptr (blocking); uint8[m] of 0 / 1."""
+    return _sorted_search(seg, lambda o: binary_search_async(seg, dtype, hay_ptr, n, needles_ptr, m, o), m, np.uint8)

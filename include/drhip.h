@@ -514,6 +514,40 @@ int drhip_max_element(int seg, int dtype, const void *x, size_t n, uint64_t *ind
 /* idx2[0] = first least, idx2[1] = LAST greatest (std::minmax_element), one read of x */
 int drhip_minmax_element(int seg, int dtype, const void *x, size_t n, uint64_t *idx2);
 
+/* ---------------------------------------------------- sorted search ----
+ * std::lower_bound, std::upper_bound and std::binary_search of a batch of m
+ * needles in a haystack of n elements sorted under the C++ < of the element
+ * type (what drhip_sort leaves behind; -0.0 and +0.0 are equal, +-inf are
+ * ordinary values).  Absent from the reference; what they replace is a copy
+ * of the segment to the host and a host loop.
+ * Kernel: include/dr/details/bsearch_kernel.hpp.
+ *   pos[i]   = the least p in [0, n] with !(hay[p] < needles[i])  (lower)
+ *            = the least p in [0, n] with needles[i] < hay[p]     (upper)
+ *   found[i] = 1 if some hay[p] is neither below nor above needles[i], else 0
+ * A NaN in the haystack or the needles, or a haystack that is not sorted,
+ * gives unspecified results; every pos[i] is still in [0, n], every found[i]
+ * in {0, 1} and no read leaves hay[0, n): a search is a loop of fixed trip
+ * count over clamped indices, never a data-dependent walk.
+ * Every workgroup first copies DRHIP_SORTED_SEARCH_STAGE(element bytes) evenly
+ * spaced haystack elements to LDS and resolves the top levels of every search
+ * there; with m below that number the staging is skipped.
+ * Asynchronous on the segment's stream.  hay and needles: n and m elements of
+ * dtype; pos: m uint64, found: m uint8; all device-visible.  m == 0 returns
+ * DRHIP_OK and touches nothing; n == 0 with m > 0 writes m zeros.
+ * DRHIP_ERR_BAD_ARG: an unknown dtype, a null hay with n > 0, null needles or
+ * output with m > 0, n >= 2^32 or m >= 2^32, and an output that overlaps hay
+ * or needles (their full extents); the arguments are checked before the
+ * segment, so a refusal leaves the output untouched.
+ * The kernel keeps NO state in the segment's workspace: it reads hay and
+ * needles and writes the output, nothing else.  A call can therefore be
+ * captured between drhip_graph_begin and drhip_graph_end without an eager
+ * warm-up call, and a replay recomputes everything from the buffers'
+ * contents at that time. */
+#define DRHIP_SORTED_SEARCH_STAGE(elem_bytes) ((elem_bytes) <= 4 ? 8192 : 8192)
+int drhip_lower_bound(int seg, int dtype, const void *hay, size_t n, const void *needles, size_t m, uint64_t *pos);
+int drhip_upper_bound(int seg, int dtype, const void *hay, size_t n, const void *needles, size_t m, uint64_t *pos);
+int drhip_binary_search(int seg, int dtype, const void *hay, size_t n, const void *needles, size_t m, uint8_t *found);
+
 /* ---------------------------------------------------------- stencil ----
  * mhp::transform of a radius-r 1-D stencil over a halo'd segment
  * (mhp/algorithms/cpu_algorithms.hpp:147-161 with the ops of
