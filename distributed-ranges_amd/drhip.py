@@ -63,6 +63,7 @@ EXPORTS = [
     "drhip_find_if", "drhip_is_sorted_until", "drhip_mismatch",
     "drhip_min_element", "drhip_max_element", "drhip_minmax_element",
     "drhip_lower_bound", "drhip_upper_bound", "drhip_binary_search",
+    "drhip_merge", "drhip_merge_pairs",
     "drhip_comm_unique_id", "drhip_comm_init_rank", "drhip_comm_init_all", "drhip_comm_destroy",
     "drhip_comm_rank", "drhip_comm_group_start", "drhip_comm_group_end", "drhip_allreduce",
     "drhip_allgather", "drhip_gather", "drhip_alltoallv", "drhip_halo_exchange",
@@ -135,6 +136,8 @@ def load():
         "drhip_max_element": [i, i, vp, sz, vp], "drhip_minmax_element": [i, i, vp, sz, vp],
         "drhip_lower_bound": [i, i, vp, sz, vp, sz, vp], "drhip_upper_bound": [i, i, vp, sz, vp, sz, vp],
         "drhip_binary_search": [i, i, vp, sz, vp, sz, vp],
+        "drhip_merge": [i, i, vp, sz, vp, sz, vp],
+        "drhip_merge_pairs": [i, i, vp, vp, sz, vp, vp, sz, sz, vp, vp],
         "drhip_comm_unique_id": [vp], "drhip_comm_init_rank": [i, i, i, vp], "drhip_comm_init_all": [],
         "drhip_comm_destroy": [i], "drhip_comm_rank": [i, vp, vp], "drhip_comm_group_start": [],
         "drhip_comm_group_end": [], "drhip_allreduce": [i, i, i, vp, vp, sz], "drhip_allgather": [i, vp, vp, sz],
@@ -522,6 +525,21 @@ def binary_search_async(seg, dtype, hay, n, needles, m, found_dev):
     check(load().drhip_binary_search(seg, DTYPES[np.dtype(dtype)], hay, n, needles, m, found_dev))
 
 
+# The outputs per tile of the merge, by element bytes (DRHIP_MERGE_TILE of drhip.h).
+MERGE_TILE = {4: 2048, 8: 2048}
+
+
+def merge_async(seg, dtype, a, na, b, nb, out_dev):
+    """drhip_merge: out_dev[0, na + nb) = the stable merge (a first on ties) of the sorted a[0, na) and b[0, nb)."""
+    check(load().drhip_merge(seg, DTYPES[np.dtype(dtype)], a, na, b, nb, out_dev))
+
+
+def merge_pairs_async(seg, kdtype, a_keys, a_vals, na, b_keys, b_vals, nb, val_bytes, out_keys, out_vals):
+    """drhip_merge_pairs: drhip_merge of the keys, every key's value (val_bytes = 4 or 8 opaque bytes) moving with it."""
+    check(load().drhip_merge_pairs(seg, DTYPES[np.dtype(kdtype)], a_keys, a_vals, na, b_keys, b_vals, nb, val_bytes,
+                                   out_keys, out_vals))
+
+
 def _op(op):
     return OPS[op] if isinstance(op, str) else int(op)
 
@@ -802,3 +820,26 @@ def upper_bound(seg, hay_ptr, n, needles_ptr, m, dtype):
 def binary_search(seg, hay_ptr, n, needles_ptr, m, dtype):
     """Whether each of the m needles is in the sorted n elements at hay_ptr (blocking); uint8[m] of 0 / 1."""
     return _sorted_search(seg, lambda o: binary_search_async(seg, dtype, hay_ptr, n, needles_ptr, m, o), m, np.uint8)
+
+
+def merge(seg, a_ptr, na, b_ptr, nb, dtype):
+    """The stable merge of the sorted na elements at a_ptr and nb elements at b_ptr (blocking); dtype[na + nb]."""
+    out = DeviceArray(seg, na + nb, dtype)
+    try:
+        merge_async(seg, dtype, a_ptr, na, b_ptr, nb, out.ptr)
+        return out.numpy()
+    finally:
+        out.free()
+
+
+def merge_pairs(seg, a_keys_ptr, a_vals_ptr, na, b_keys_ptr, b_vals_ptr, nb, kdtype, vdtype):
+    """merge() of the keys with one value of vdtype (4 or 8 bytes) per key (blocking); (keys, values)."""
+    keys = DeviceArray(seg, na + nb, kdtype)
+    vals = DeviceArray(seg, na + nb, vdtype)
+    try:
+        merge_pairs_async(seg, kdtype, a_keys_ptr, a_vals_ptr, na, b_keys_ptr, b_vals_ptr, nb, np.dtype(vdtype).itemsize,
+                          keys.ptr, vals.ptr)
+        return keys.numpy(), vals.numpy()
+    finally:
+        keys.free()
+        vals.free()

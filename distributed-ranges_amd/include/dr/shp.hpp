@@ -13,6 +13,7 @@
 #include "shp/scan_by_key.hpp"
 #include "shp/search.hpp"
 #include "shp/sorted_search.hpp"
+#include "shp/merge.hpp"
 #include "shp/vector.hpp"
 #include "shp/sparse.hpp"
 #include "shp/dense.hpp"

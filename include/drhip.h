@@ -548,6 +548,42 @@ int drhip_lower_bound(int seg, int dtype, const void *hay, size_t n, const void 
 int drhip_upper_bound(int seg, int dtype, const void *hay, size_t n, const void *needles, size_t m, uint64_t *pos);
 int drhip_binary_search(int seg, int dtype, const void *hay, size_t n, const void *needles, size_t m, uint8_t *found);
 
+/* ------------------------------------------------------------ merge ----
+ * std::merge of two ranges sorted under the C++ < of the element type (what
+ * drhip_sort leaves behind; NOT radix order: -0.0 and +0.0 are a tie, +-inf
+ * are ordinary values), optionally carrying one value per key
+ * (thrust::merge_by_key).  Absent from the reference; what it replaces is a
+ * concatenation and another drhip_sort.
+ * Kernel: include/dr/details/merge_kernel.hpp.
+ *   out[d] = element d of the stable merge of a[0, na) and b[0, nb): on ties
+ *   a's element comes first (so a's zero precedes b's whatever their signs)
+ *   and each input keeps its own order.  drhip_merge_pairs moves the value
+ *   of every key with it, as val_bytes (4 or 8) opaque bytes.
+ * The output is cut into tiles of DRHIP_MERGE_TILE(element bytes) elements;
+ * persistent workgroups take contiguous runs of tiles, find each tile's split
+ * on the merge path themselves (a wave-wide search of global memory), stage
+ * the two pieces in LDS and merge them there.
+ * A NaN, or an input that is not sorted, gives unspecified output values; the
+ * searches are bounded loops over indices that cannot leave their interval,
+ * so no read leaves a[0, na) or b[0, nb) and exactly out[0, na + nb) is
+ * written, each element once.
+ * Asynchronous on the segment's stream.  All buffers device-visible.
+ * na + nb == 0 returns DRHIP_OK and touches nothing; with one input empty
+ * the call is a copy of the other.
+ * DRHIP_ERR_BAD_ARG: an unknown dtype, val_bytes outside {4, 8}, a null
+ * pointer with a non-zero length, na + nb >= 2^32, and any output that
+ * overlaps any input or the other output (their full extents); the arguments
+ * are checked before the segment, so a refusal leaves the outputs untouched.
+ * The kernel keeps NO state in the segment's workspace: no partition array,
+ * no counters.  A call can therefore be captured between drhip_graph_begin
+ * and drhip_graph_end without an eager warm-up call, and a replay recomputes
+ * everything from the buffers' contents at that time. */
+#define DRHIP_MERGE_TILE(elem_bytes) ((elem_bytes) <= 4 ? 2048 : 2048)
+int drhip_merge(int seg, int dtype, const void *a, size_t na, const void *b, size_t nb, void *out);
+int drhip_merge_pairs(int seg, int kdtype, const void *a_keys, const void *a_vals, size_t na,
+                      const void *b_keys, const void *b_vals, size_t nb, size_t val_bytes,
+                      void *out_keys, void *out_vals);
+
 /* ---------------------------------------------------------- stencil ----
  * mhp::transform of a radius-r 1-D stencil over a halo'd segment
  * (mhp/algorithms/cpu_algorithms.hpp:147-161 with the ops of
